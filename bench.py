@@ -1,7 +1,14 @@
 """Benchmark: device-resident distributed fp64 GEMV (BASELINE.json metric) on N MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--alg rowwise|colwise|blockwise]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (N > 1)
+
+A plain run is the headline alone: set-up, settle and warm-up, the K timed steps, one JSON line
+(`value`, `ms_per_step`, `roofline` from the timed steps' own HIP events). --dump-outputs DIR
+also writes the y of the last timed step (rank 0's, as collect() returns it) to DIR/y.npy; the
+inputs are the same on every run with the same arguments. Everything under "Also reported" below
+runs only with --full.
 
 Workload (BASELINE.json configs[1], weak-scaled): every GPU owns a 16384 x 16384 fp64 row
 shard of a (16384*N) x 16384 matrix (N = 1: exactly config 2, "Square N=16384 fp64 row-split
@@ -10,7 +17,8 @@ one pass of the hot path: the HIP GEMV on every shard + the RCCL exchange (ncclG
 to rank 0). K steps are timed between barrier + device synchronize on both sides; the time
 is the max over ranks; value = algorithmic bytes of all ranks / that time.
 
-Also reported: `roofline` (the GEMV kernel alone: bytes per launch / its mean duration from
+Also reported (all but `roofline` with --full only): `roofline` (the GEMV kernel alone:
+bytes per launch / its mean duration from
 HIP events on the engine stream — at one rank one event pair spanning the timed GEMVs, at N > 1
 every 5th step's GEMV bracketed; peak 8 TB/s; `traffic` from the committed rocprofv3 PMC
 summary when one matches this configuration), `cpu_baseline` (rank 0 at N = 1: the real
@@ -124,7 +132,23 @@ def parse():
     ap.add_argument("--no-loader", action="store_true", help="skip the text-loader section")
     ap.add_argument("--no-exact", action="store_true",
                     help="skip the bit-exact section (the same workload with mvg_engine_set_exact)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every supplementary section (exact, cpu_baseline, configs, "
+                         "end_to_end, multi_vector, loader, the reference-row checks, the runtime / rccl / "
+                         "single_process records), each within --budget-s; without it the run sets up, warms up, "
+                         "times the K steps and prints the headline's line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed, y as the caller of the "
+                         "engine receives it on rank 0, to DIR/y.npy (float64); the inputs are the same synthetic "
+                         "values on every run with the same arguments")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run is the headline alone: every section after it is one of --full's
+        args.no_exact = args.no_cpu_baseline = args.no_configs = args.no_e2e = True
+        args.no_multi = args.no_loader = True
+    return args
 
 
 def log(*a):
@@ -497,7 +521,7 @@ def main():
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     rccl_log, caller_debug = None, os.environ.get("NCCL_DEBUG")
     caller_nccl = {k: os.environ.get(k) for k in ("NCCL_DEBUG", "NCCL_DEBUG_SUBSYS", "NCCL_DEBUG_FILE")}
-    if world > 1 and "NCCL_DEBUG_FILE" not in os.environ:
+    if args.full and world > 1 and "NCCL_DEBUG_FILE" not in os.environ:
         rccl_log = f"/tmp/mvg_rccl_{os.environ.get('MASTER_PORT', '0')}_{os.environ.get('RANK', '0')}.log"
         os.environ.update(NCCL_DEBUG="INFO", NCCL_DEBUG_SUBSYS="INIT,P2P", NCCL_DEBUG_FILE=rccl_log)
     import torch
@@ -597,6 +621,9 @@ def main():
     # [0, 0.9999]); exact parity is checked against the reference restatement in cpu_baseline
     # (N = 1) and by tests/.
     y = eng.collect()
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "y.npy"), np.asarray(y, dtype=np.float64))
     if rank == 0:
         expect(np.all(np.isfinite(y)) and y.min() >= 0.0 and y.max() <= C * 0.9999 ** 2, "y out of range")
         pmc = pmc_summary(sh.n_rows, sh.n_cols, kernel_name(sh)) or {}
@@ -717,10 +744,10 @@ def main():
         report["loader"] = section("loader", est_loader(R, C), loader_section, R, C, collective=False)
 
     budget.current = "teardown"
-    rccl = rccl_report(rccl_log, distributed, rank) if distributed else None
+    rccl = rccl_report(rccl_log, distributed, rank) if distributed and args.full else None
     if rccl is not None:
         rccl["caller_NCCL_DEBUG"] = caller_debug
-    if rank == 0:
+    if rank == 0 and args.full:
         from matvec_mpi_multiplier_amd._lib import runtime_info
 
         # the RCCL and HIP runtime the rank sections ran on (PyTorch's bundled copies when the
@@ -741,7 +768,7 @@ def main():
         dist.destroy_process_group()
     budget.current = None
     if rank == 0:
-        if n > 1:
+        if n > 1 and args.full:
             # the executables' one-process-drives-N-GPUs path (ncclCommInitAll, grouped exchange),
             # which the rank-per-GPU sections above never run; the other ranks have exited
             if single_process_blocker(n):  # nothing to run here: record why, whatever the budget
@@ -753,7 +780,7 @@ def main():
             if isinstance(sp, dict) and sp.get("error"):
                 WARNINGS.append(f"single_process: the MVG_NGPUS={n} executable failed (rc {sp.get('rc')}): "
                                 f"{sp['error'][-200:]}")
-        else:
+        elif args.full:
             report["single_process"] = None
         report.write()
     if FAILURES:

@@ -223,8 +223,8 @@ def test_bench_two_ranks_one_device(tmp_path):
     env = dict(os.environ, MVG_SAME_DEVICE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--e2e-iters", "1", "--config-steps", "2",
-                        "--config-e2e", "5"],
+                        "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--e2e-iters", "1",
+                        "--config-steps", "2", "--config-e2e", "5"],
                        cwd=tmp_path, env=env, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -355,7 +355,7 @@ def test_bench_sigterm_mid_run_keeps_the_line(tmp_path):
     import time
 
     p = subprocess.Popen([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2",
-                          "--no-cpu-baseline", "--configs", "3,4", "--config-e2e", "4"],
+                          "--full", "--no-cpu-baseline", "--configs", "3,4", "--config-e2e", "4"],
                          cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     seen = threading.Event()
     err = []
@@ -384,3 +384,35 @@ def test_bench_sigterm_mid_run_keeps_the_line(tmp_path):
     assert d["value"] > 0 and d["roofline"]["frac"] > 0 and d["exact"]["value"] > 0
     assert [c["config"] for c in d["configs"]] == ["config 3"]  # config 4 had not finished
     assert "headline" in d["sections_s"] and "config 3" in d["sections_s"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_y(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline's fields and nothing that
+    takes a run of its own; --dump-outputs writes the last timed step's y (the seeded synthetic
+    inputs, so the oracle's y for the same A and x within the parity bar)."""
+    import json
+
+    from oracle import oracle
+
+    R, C = 1000, 1537  # no multiple of a tile either way; a second's work for the oracle
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--rows", str(R), "--cols", str(C), "--settle-s", "0", "--dump-outputs", str(out)],
+                       cwd=tmp_path, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "GB/s"
+    assert d["dtype"] == "f64" and d["higher_is_better"] is True and d["failures"] is None
+    assert abs(d["value"] - d["config"]["bytes_per_step"] / (d["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * d["value"]
+    for key in ("exact", "cpu_baseline", "configs", "end_to_end", "multi_vector", "loader", "reference_rows",
+                "runtime", "single_process"):
+        assert key not in d, key
+    assert set(d["sections_s"]) == {"setup_and_headline", "headline"}
+    assert sorted(os.listdir(out)) == ["y.npy"]
+    y = np.load(out / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (R,)
+    want = oracle.multiply("rowwise", oracle.synth(R, C, 42), oracle.synth(1, C, 4242)[0], 1)
+    assert max_rel(y, want) <= 1e-12

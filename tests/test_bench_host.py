@@ -712,3 +712,20 @@ def test_executable_runtime_names_the_executables_rccl():
     if r is None:
         pytest.skip("bin/multiplier_rowwise not built")
     assert r["rccl_origin"] == "rocm" and r["rccl_version"].count(".") == 2 and r["hip_origin"] == "rocm"
+
+
+def test_plain_run_skips_every_supplementary_section(monkeypatch):
+    """Without --full the parsed arguments switch every section after the headline off; --full
+    leaves them as given (its own --no-* switches still apply)."""
+    flags = ("no_exact", "no_cpu_baseline", "no_configs", "no_e2e", "no_multi", "no_loader")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert all(getattr(a, f) for f in flags)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-loader", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_loader
+    assert not any(getattr(a, f) for f in flags if f != "no_loader")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

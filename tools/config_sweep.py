@@ -37,7 +37,7 @@ def main():
         for name, cargs in CONFIGS.items():
             if only and name not in only:
                 continue
-            cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(args.gpus)] + cargs + extra
+            cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", str(args.gpus)] + cargs + extra
             if args.gpus > 1:
                 cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                        "--master-addr", "127.0.0.1", "--master-port", "29512"] + cmd[1:]

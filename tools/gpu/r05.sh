@@ -30,12 +30,12 @@ for step in $STEPS; do
     tail -2 $OUT/smoke.log; ok $rc || exit $rc ;;
   bench)
     echo "== bench N=1 (the driver's command)"
-    timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+    timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; rc=$?
     tail -c 300 $OUT/bench.json; tail -3 $OUT/bench.err; ok $rc || exit $rc ;;
   benchprof)
     echo "== bench N=1 under rocprofv3 --kernel-trace --stats"
     cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o run -- \
-        python3 $ROOT/bench.py --steps 20 --warmup 5 > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err; rc=$?
+        python3 $ROOT/bench.py --full --steps 20 --warmup 5 > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err; rc=$?
     cd $ROOT; ok $rc || { tail $OUT/bench_prof.err; exit $rc; }
     python3 tools/rocprof_by_grid.py $OUT/prof --out $OUT/kernel_by_grid.csv ;;
   pmc)
@@ -118,22 +118,22 @@ for l in open('$OUT/evcost.jsonl'):
     d = json.loads(l); print(d['roofline']['kernel_ms'], d['value'], d['ms_per_step'], (d.get('settle') or {}).get('last_us_per_step'))" ;;
   rehearse8)
     echo "== N=8 same-device rehearsal with a 120 s budget (the launcher-free form: bench.py starts the ranks)"
-    MVG_SAME_DEVICE=1 timeout -k 30 400 python3 bench.py --gpus 8 --steps 5 --warmup 2 --budget-s 120 \
+    MVG_SAME_DEVICE=1 timeout -k 30 400 python3 bench.py --full --gpus 8 --steps 5 --warmup 2 --budget-s 120 \
         > $OUT/bench_n8.json 2> $OUT/bench_n8.err; rc=$?
     tail -c 400 $OUT/bench_n8.json; grep "bench:" $OUT/bench_n8.err | tail -5; ok $rc || exit $rc ;;
   rehearse4)
     echo "== N=4 same-device rehearsal with the driver's defaults (budget 420 s): the whole line within the limit"
-    MVG_SAME_DEVICE=1 timeout -k 30 600 python3 bench.py --gpus 4 --steps 20 --warmup 5 \
+    MVG_SAME_DEVICE=1 timeout -k 30 600 python3 bench.py --full --gpus 4 --steps 20 --warmup 5 \
         > $OUT/bench_n4.json 2> $OUT/bench_n4.err; rc=$?
     tail -c 600 $OUT/bench_n4.json; grep "bench:" $OUT/bench_n4.err | tail -8; ok $rc || exit $rc ;;
   rehearse8d)
     echo "== N=8 same-device rehearsal with the driver's defaults (budget 420 s; loopback sockets: the worst case)"
-    MVG_SAME_DEVICE=1 timeout -k 30 700 python3 bench.py --gpus 8 --steps 20 --warmup 5 \
+    MVG_SAME_DEVICE=1 timeout -k 30 700 python3 bench.py --full --gpus 8 --steps 20 --warmup 5 \
         > $OUT/bench_n8d.json 2> $OUT/bench_n8d.err; rc=$?
     tail -c 600 $OUT/bench_n8d.json; grep "bench:" $OUT/bench_n8d.err | tail -8; ok $rc || exit $rc ;;
   sigterm8)
     echo "== N=8 same-device run terminated by a time limit mid-run: the line so far must come out (last step)"
-    MVG_SAME_DEVICE=1 timeout -s TERM -k 60 75 python3 bench.py --gpus 8 --steps 5 --warmup 2 \
+    MVG_SAME_DEVICE=1 timeout -s TERM -k 60 75 python3 bench.py --full --gpus 8 --steps 5 --warmup 2 \
         > $OUT/bench_n8_sigterm.json 2> $OUT/bench_n8_sigterm.err; rc=$?
     echo "rc=$rc"; tail -c 600 $OUT/bench_n8_sigterm.json; grep "bench:" $OUT/bench_n8_sigterm.err | tail -5
     exit 0 ;;

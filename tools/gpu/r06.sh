@@ -70,7 +70,7 @@ for l in open('$OUT/host_setup.jsonl'):
   bench2)
     echo "== bench N=1 twice back to back, no CPU sections (the second starts while the first's VRAM is being cleared)"
     for i in 1 2; do
-      timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-multi --no-loader \
+      timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-e2e --no-multi --no-loader \
           > $OUT/bench2_$i.json 2> $OUT/bench2_$i.err; rc=$?; ok $rc || exit $rc
       python3 -c "
 import json
@@ -79,28 +79,28 @@ print($i, p['value'], p['roofline']['frac'], p.get('vram_wait'), [(c['config'], 
     done ;;
   bench)
     echo "== bench N=1 (the driver's command)"
-    timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; rc=$?
+    timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; rc=$?
     tail -c 300 $OUT/bench.json; tail -3 $OUT/bench.err; ok $rc || exit $rc ;;
   benchprof)
     echo "== bench N=1 under rocprofv3 --kernel-trace --stats"
     cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o run -- \
-        python3 $ROOT/bench.py --steps 20 --warmup 5 > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err; rc=$?
+        python3 $ROOT/bench.py --full --steps 20 --warmup 5 > $ROOT/$OUT/bench_prof.json 2> $ROOT/$OUT/bench_prof.err; rc=$?
     cd $ROOT; ok $rc || { tail $OUT/bench_prof.err; exit $rc; }
     python3 tools/rocprof_by_grid.py $OUT/prof --out $OUT/kernel_by_grid.csv ;;
   rehearse4)
     echo "== N=4 same-device rehearsal with the driver's defaults (budget 420 s)"
-    MVG_SAME_DEVICE=1 timeout -k 30 600 python3 bench.py --gpus 4 --steps 20 --warmup 5 \
+    MVG_SAME_DEVICE=1 timeout -k 30 600 python3 bench.py --full --gpus 4 --steps 20 --warmup 5 \
         > $OUT/bench_n4.json 2> $OUT/bench_n4.err; rc=$?
     tail -c 600 $OUT/bench_n4.json; grep "bench:" $OUT/bench_n4.err | tail -8; ok $rc || exit $rc ;;
   rehearse2l)
     echo "== N=2 same-device rehearsal, the driver's own launcher command, default budget"
     MVG_SAME_DEVICE=1 timeout -k 30 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 \
+        --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 5 \
         > $OUT/bench_n2.json 2> $OUT/bench_n2.err; rc=$?
     tail -c 600 $OUT/bench_n2.json; grep "bench:" $OUT/bench_n2.err | tail -8; ok $rc || exit $rc ;;
   rehearse8d)
     echo "== N=8 same-device rehearsal with the driver's defaults (budget 420 s; loopback sockets: the worst case)"
-    MVG_SAME_DEVICE=1 timeout -k 30 700 python3 bench.py --gpus 8 --steps 20 --warmup 5 \
+    MVG_SAME_DEVICE=1 timeout -k 30 700 python3 bench.py --full --gpus 8 --steps 20 --warmup 5 \
         > $OUT/bench_n8d.json 2> $OUT/bench_n8d.err; rc=$?
     tail -c 600 $OUT/bench_n8d.json; grep "bench:" $OUT/bench_n8d.err | tail -8; ok $rc || exit $rc ;;
   esac

@@ -14,6 +14,6 @@ echo "== bench under rocprofv3"
 ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o run -- \
-    python3 $ROOT/bench.py > $ROOT/$OUT/bench.json 2> $ROOT/$OUT/bench.err || { tail $ROOT/$OUT/bench.err; exit 1; }
+    python3 $ROOT/bench.py --full > $ROOT/$OUT/bench.json 2> $ROOT/$OUT/bench.err || { tail $ROOT/$OUT/bench.err; exit 1; }
 cd $ROOT
 tail -c 400 $OUT/bench.json
