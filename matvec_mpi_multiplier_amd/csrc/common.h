@@ -31,6 +31,32 @@ int take_pending_error(const char* where);
         if (_e != hipSuccess) return ::mvg::hip_fail(_e, #call);          \
     } while (0)
 
+// ----- variant tables (gemv.hip, gemv_exact.hip)
+// Variants are addressed by name, resolved at compile time: inserting or removing a table
+// entry cannot send a shape to the wrong kernel (a missing name fails the build).
+constexpr bool name_eq(const char* a, const char* b) {
+    while (*a && *a == *b) ++a, ++b;
+    return *a == *b;
+}
+template <typename T, size_t N>
+constexpr int variant_id(const T (&table)[N], const char* name) {
+    for (size_t i = 0; i < N; ++i)
+        if (name_eq(table[i].name, name)) return (int)i;
+    return -1;
+}
+
+// Short rows (K <= 768) go out in launches of at most 1 GiB of A, for the tree form's one-row
+// waves and the exact forms alike (the measurements stand at the two launch loops): 1 GiB of the
+// bytes read, k per row — a view's wider lda does not shrink the pieces — and never under 65536
+// rows, so a launch still fills the chip; whole workgroups of rows_per_block rows.
+constexpr int64_t kOneRowLaunchBytes = 1ll << 30;
+constexpr int64_t kMinPieceRows = 65536;
+inline int64_t short_row_piece_rows(int64_t k, int rows_per_block) {
+    int64_t cap = kOneRowLaunchBytes / (k * (int64_t)sizeof(double));
+    if (cap < kMinPieceRows) cap = kMinPieceRows;
+    return cap / rows_per_block * rows_per_block;
+}
+
 // ----- exact exchange (gemv_exact.hip): the reference's own combine orders on the root
 // MPI_Reduce(SUM) as the reference's MPICH runs it (colwise.c:124): binomial tree or, for long
 // buffers, reduce-scatter + gather, by MPICH 3.3.2's own rule (gemv_exact.hip); overwrites parts

@@ -124,6 +124,62 @@ __device__ __forceinline__ void fma_chunk(double (&acc)[RPG], const dbl2 (&xv)[U
         }
 }
 
+// ------------------------------------------------------------------ shared pieces
+// What the kernel families below have in common. The helpers take the arrays by reference and
+// lane / wave as arguments and keep the statements in the order the kernels had them: the
+// kernels are register-tight, and the allocation follows the form of the code. The
+// double-buffered chunk loops stay written out in their kernels: inside an inlined driver the
+// compiler optimises them before they meet the kernel and then pipelines either every
+// instantiation or none (gemv_rowblock<8,2,8> 142 -> 216 VGPRs, or <4,2,8> 218 -> 142;
+// MEASUREMENTS §10). row_ptr returns its pointer for the same reason: filling arow[] through a
+// reference reordered the address code of some forty kernels.
+
+// Row `row` of A, clamped: an out-of-range row re-reads the last valid row and is never stored.
+__device__ __forceinline__ const double* row_ptr(const double* A, int64_t lda, int64_t row, int64_t M) {
+    const int64_t rr = row < M ? row : M - 1;
+    return A + rr * lda;
+}
+
+// One step of the column tail, single vector (mtail is the multi-vector one): the pair at
+// columns c, c + 1, or the last odd column.
+template <int RPG, bool NT>
+__device__ __forceinline__ void tail_step(double (&acc)[RPG], const double* const (&arow)[RPG], const double* x,
+                                          int64_t c, int64_t K) {
+    if (c + 1 < K) {
+        const dbl2 xv = load2<false>(x + c);
+#pragma unroll
+        for (int r = 0; r < RPG; ++r) {
+            const dbl2 a = load2<NT>(arow[r] + c);
+            acc[r] = __builtin_fma(a.x, xv.x, acc[r]);
+            acc[r] = __builtin_fma(a.y, xv.y, acc[r]);
+        }
+    } else {
+        const double xs = x[c];
+#pragma unroll
+        for (int r = 0; r < RPG; ++r) acc[r] = __builtin_fma(arow[r][c], xs, acc[r]);
+    }
+}
+
+// Reduction of the workgroup-sweeps-rows kernels: each wave's sum of acc[r] (DPP) goes to
+// part[w][r]; after the barrier thread r < RPB, if live(r), adds the NW partials in wave order
+// (fixed, deterministic) and hands the sum to store(r, s).
+template <int NW, int RPB, class LIVE, class STORE>
+__device__ __forceinline__ void reduce_block_rows(const double (&acc)[RPB], double (&part)[NW][RPB], int lane, int w,
+                                                  LIVE&& live, STORE&& store) {
+#pragma unroll
+    for (int r = 0; r < RPB; ++r) {
+        const double s = group_sum_dpp<64>(acc[r]);
+        if (lane == 0) part[w][r] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < RPB && live(threadIdx.x)) {
+        double s = 0.0;
+#pragma unroll
+        for (int v = 0; v < NW; ++v) s += part[v][threadIdx.x];
+        store(threadIdx.x, s);
+    }
+}
+
 // 16-B path (A and x 8-B aligned; fastest with an even lda and 16-B aligned A, x).
 template <int LPR, int RPG, int UNR, bool NT, int OPT>
 __global__ __launch_bounds__(kBlock) void gemv_vec(const double* __restrict__ A, int64_t lda,
@@ -139,11 +195,7 @@ __global__ __launch_bounds__(kBlock) void gemv_vec(const double* __restrict__ A,
 
     const double* arow[RPG];
 #pragma unroll
-    for (int r = 0; r < RPG; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;  // clamp: out-of-range rows re-read a valid row, never stored
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPG; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     double acc[RPG];
 #pragma unroll
     for (int r = 0; r < RPG; ++r) acc[r] = 0.0;
@@ -190,21 +242,7 @@ __global__ __launch_bounds__(kBlock) void gemv_vec(const double* __restrict__ A,
         }
     }
     // column tail: whole pairs, then a possible last odd column
-    for (int64_t c = kmain + c0; c < K; c += kStep) {
-        if (c + 1 < K) {
-            const dbl2 xv = load2<false>(x + c);
-#pragma unroll
-            for (int r = 0; r < RPG; ++r) {
-                const dbl2 a = load2<NT>(arow[r] + c);
-                acc[r] = __builtin_fma(a.x, xv.x, acc[r]);
-                acc[r] = __builtin_fma(a.y, xv.y, acc[r]);
-            }
-        } else {
-            const double xs = x[c];
-#pragma unroll
-            for (int r = 0; r < RPG; ++r) acc[r] = __builtin_fma(arow[r][c], xs, acc[r]);
-        }
-    }
+    for (int64_t c = kmain + c0; c < K; c += kStep) tail_step<RPG, NT>(acc, arow, x, c, K);
 #pragma unroll
     for (int r = 0; r < RPG; ++r) {
         const double s = (OPT & kDpp) != 0 ? group_sum_dpp<LPR>(acc[r]) : group_sum<LPR>(acc[r]);
@@ -254,11 +292,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock(const double* __restric
     const int64_t row0 = bid * RPB;
     const double* arow[RPB];
 #pragma unroll
-    for (int r = 0; r < RPB; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPB; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     double acc[RPB];
 #pragma unroll
     for (int r = 0; r < RPB; ++r) acc[r] = 0.0;
@@ -287,33 +321,10 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock(const double* __restric
         if (i < nch) fma_chunk<RPB, UNR>(acc, xa, aa);
     }
     // column tail (K % kChunk), spread over the whole workgroup
-    for (int64_t c = nch * kChunk + 2 * (int64_t)threadIdx.x; c < K; c += 2 * NW * 64) {
-        if (c + 1 < K) {
-            const dbl2 xv = load2<false>(x + c);
-#pragma unroll
-            for (int r = 0; r < RPB; ++r) {
-                const dbl2 a = load2<NT>(arow[r] + c);
-                acc[r] = __builtin_fma(a.x, xv.x, acc[r]);
-                acc[r] = __builtin_fma(a.y, xv.y, acc[r]);
-            }
-        } else {
-            const double xs = x[c];
-#pragma unroll
-            for (int r = 0; r < RPB; ++r) acc[r] = __builtin_fma(arow[r][c], xs, acc[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RPB; ++r) {
-        const double s = group_sum_dpp<64>(acc[r]);
-        if (lane == 0) part[w][r] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPB && row0 + threadIdx.x < M) {
-        double s = 0.0;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) s += part[v][threadIdx.x];
-        y[row0 + threadIdx.x] = s;
-    }
+    for (int64_t c = nch * kChunk + 2 * (int64_t)threadIdx.x; c < K; c += 2 * NW * 64)
+        tail_step<RPB, NT>(acc, arow, x, c, K);
+    reduce_block_rows<NW, RPB>(
+        acc, part, lane, w, [&](int r) { return row0 + r < M; }, [&](int r, double s) { y[row0 + r] = s; });
 }
 
 // Row-per-workgroup form for rows that do not start on 128-B lines (an lda that is not a
@@ -342,7 +353,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock_lines(const double* __r
     const int64_t row_of[RPB] = {bid / p * 2 * p + bid % p, bid / p * 2 * p + bid % p + p};
     const double* arow[RPB];
 #pragma unroll
-    for (int r = 0; r < RPB; ++r) arow[r] = A + (row_of[r] < M ? row_of[r] : M - 1) * lda;
+    for (int r = 0; r < RPB; ++r) arow[r] = row_ptr(A, lda, row_of[r], M);
     int64_t h = (int64_t)(((128u - ((uintptr_t)arow[0] & 127u)) & 127u) >> 3);
     h = h < K ? h : K;
     double acc[RPB];
@@ -353,7 +364,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock_lines(const double* __r
     const double* xs = x + h;
     const int64_t Kh = K - h;
 
-    constexpr int64_t kStep = 128;
+    constexpr int64_t kStep = 128;            // columns per wave per sub-step (64 lanes x 2)
     constexpr int64_t kChunk = kStep * UNR;
     const int64_t nch = Kh / kChunk;
     const int64_t c0 = 2 * lane;
@@ -370,39 +381,17 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock_lines(const double* __r
                 fma_chunk<RPB, UNR>(acc, xb, ab);
             } else {
                 fma_chunk<RPB, UNR>(acc, xb, ab);
-                i = nch;
+                i = nch;  // both buffers consumed
                 break;
             }
         }
         if (i < nch) fma_chunk<RPB, UNR>(acc, xa, aa);
     }
-    for (int64_t c = nch * kChunk + 2 * (int64_t)threadIdx.x; c < Kh; c += 2 * NW * 64) {
-        if (c + 1 < Kh) {
-            const dbl2 xv = load2<false>(xs + c);
-#pragma unroll
-            for (int r = 0; r < RPB; ++r) {
-                const dbl2 a = load2<NT>(arow[r] + c);
-                acc[r] = __builtin_fma(a.x, xv.x, acc[r]);
-                acc[r] = __builtin_fma(a.y, xv.y, acc[r]);
-            }
-        } else {
-            const double xv = xs[c];
-#pragma unroll
-            for (int r = 0; r < RPB; ++r) acc[r] = __builtin_fma(arow[r][c], xv, acc[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RPB; ++r) {
-        const double s = group_sum_dpp<64>(acc[r]);
-        if (lane == 0) part[w][r] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPB && row_of[threadIdx.x] < M) {
-        double s = 0.0;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) s += part[v][threadIdx.x];
-        y[row_of[threadIdx.x]] = s;
-    }
+    // column tail (K % kChunk), spread over the whole workgroup
+    for (int64_t c = nch * kChunk + 2 * (int64_t)threadIdx.x; c < Kh; c += 2 * NW * 64)
+        tail_step<RPB, NT>(acc, arow, xs, c, Kh);
+    reduce_block_rows<NW, RPB>(
+        acc, part, lane, w, [&](int r) { return row_of[r] < M; }, [&](int r, double s) { y[row_of[r]] = s; });
 }
 
 // Split-K for short, wide problems (few rows, so too few row workgroups to fill 256 CUs):
@@ -428,11 +417,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock_split(const double* __r
     x += k0;
     const double* arow[RPB];
 #pragma unroll
-    for (int r = 0; r < RPB; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPB; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     double acc[RPB];
 #pragma unroll
     for (int r = 0; r < RPB; ++r) acc[r] = 0.0;
@@ -461,33 +446,11 @@ __global__ __launch_bounds__(NW * 64) void gemv_rowblock_split(const double* __r
         if (i < nch) fma_chunk<RPB, UNR>(acc, xa, aa);
     }
     // column tail (K % kChunk), spread over the whole workgroup
-    for (int64_t c = nch * kChunk + 2 * (int64_t)threadIdx.x; c < K; c += 2 * NW * 64) {
-        if (c + 1 < K) {
-            const dbl2 xv = load2<false>(x + c);
-#pragma unroll
-            for (int r = 0; r < RPB; ++r) {
-                const dbl2 a = load2<NT>(arow[r] + c);
-                acc[r] = __builtin_fma(a.x, xv.x, acc[r]);
-                acc[r] = __builtin_fma(a.y, xv.y, acc[r]);
-            }
-        } else {
-            const double xs = x[c];
-#pragma unroll
-            for (int r = 0; r < RPB; ++r) acc[r] = __builtin_fma(arow[r][c], xs, acc[r]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < RPB; ++r) {
-        const double s = group_sum_dpp<64>(acc[r]);
-        if (lane == 0) part[w][r] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < RPB && row0 + threadIdx.x < M) {
-        double s = 0.0;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) s += part[v][threadIdx.x];
-        partial[(row0 + threadIdx.x) * S + sp] = s;
-    }
+    for (int64_t c = nch * kChunk + 2 * (int64_t)threadIdx.x; c < K; c += 2 * NW * 64)
+        tail_step<RPB, NT>(acc, arow, x, c, K);
+    reduce_block_rows<NW, RPB>(
+        acc, part, lane, w, [&](int r) { return row0 + r < M; },
+        [&](int r, double s) { partial[(row0 + r) * S + sp] = s; });
 }
 
 __global__ void gemv_splitk_reduce(const double* __restrict__ partial, int64_t S,
@@ -516,11 +479,7 @@ __global__ __launch_bounds__(kBlock) void gemv_scalar(const double* __restrict__
 
     const double* arow[RPG];
 #pragma unroll
-    for (int r = 0; r < RPG; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPG; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     double acc[RPG];
 #pragma unroll
     for (int r = 0; r < RPG; ++r) acc[r] = 0.0;
@@ -665,18 +624,7 @@ static constexpr Variant kVariants[] = {
 };
 constexpr int kNumVariants = (int)(sizeof(kVariants) / sizeof(kVariants[0]));
 
-// Variants are addressed by name, resolved at compile time: inserting or removing a table
-// entry cannot send a shape to the wrong kernel (a missing name fails the build).
-constexpr bool name_eq(const char* a, const char* b) {
-    while (*a && *a == *b) ++a, ++b;
-    return *a == *b;
-}
-template <typename T, size_t N>
-constexpr int variant_id(const T (&table)[N], const char* name) {
-    for (size_t i = 0; i < N; ++i)
-        if (name_eq(table[i].name, name)) return (int)i;
-    return -1;
-}
+// the dispatch's picks, by name (variant_id, common.h)
 constexpr int kScalarLong = variant_id(kVariants, "scl_l64_r4_u4_nt1");   // 8-B path, K >= 256
 constexpr int kScalarShort = variant_id(kVariants, "scl_l16_r2_u4_nt1");  // 8-B path, K < 256
 constexpr int kSplitK = variant_id(kVariants, "rowblk_w4_r2_u4_splitk");
@@ -789,8 +737,6 @@ static int64_t split_count(const Variant& var, int64_t M, int64_t K, bool force)
 
 // HIP caps a launch at gridDim.x * blockDim.x < 2^32 threads: very tall problems run as
 // several launches over consecutive row ranges (each range is an independent GEMV).
-constexpr int64_t kOneRowLaunchBytes = 1ll << 30;
-constexpr int64_t kMinPieceRows = 65536;
 static int launch(int v, const double* A, int64_t lda, const double* x, double* y, int64_t M,
                   int64_t K, hipStream_t s, bool force_split) {
     const Variant& var = kVariants[v];
@@ -818,12 +764,9 @@ static int launch(int v, const double* A, int64_t lda, const double* x, double* 
     // 2.37-2.38 ms or 2.50-2.53 ms, the slow placement in most bench runs); 1 GiB launches run at
     // 2.34-2.36 ms on either (2.39-2.40 on some boxes' fast buffers: the extra launch boundaries),
     // and the 2 GiB shard at 292 instead of 301-310 us (round 3, profiles/r03/sublaunch/).
-    // (1 GiB of the bytes read, k per row — a view's wider lda does not shrink the pieces — and
-    // never under 65536 rows, so a launch still fills the chip)
+    // (the cap: short_row_piece_rows, common.h)
     if (v == kVecOneRow) {
-        int64_t cap = kOneRowLaunchBytes / (K * (int64_t)sizeof(double));
-        if (cap < kMinPieceRows) cap = kMinPieceRows;
-        cap = cap / var.rows_per_block * var.rows_per_block;
+        const int64_t cap = short_row_piece_rows(K, var.rows_per_block);
         if (cap < max_rows) max_rows = cap;
     }
     for (int64_t r0 = 0; r0 < M; r0 += max_rows) {
@@ -912,11 +855,7 @@ __global__ __launch_bounds__(kBlock) void gemv_mvec(const double* __restrict__ A
     const int64_t row0 = (wave * G + g) * RPG;
     const double* arow[RPG];
 #pragma unroll
-    for (int r = 0; r < RPG; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPG; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     const double* xv[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) xv[v] = X + (v < nv ? v : 0) * ldx;
@@ -973,11 +912,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mrow(const double* __restrict__ 
     const int64_t row0 = (int64_t)blockIdx.x * RPB;
     const double* arow[RPB];
 #pragma unroll
-    for (int r = 0; r < RPB; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPB; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     const double* xv[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) xv[v] = X + (v < nv ? v : 0) * ldx;
@@ -1054,11 +989,7 @@ __global__ __launch_bounds__(kBlock) void gemv_mlds(const double* __restrict__ A
     const int64_t row0 = (int64_t)blockIdx.x * (NW * RPW) + w * RPW;
     const double* arow[RPW];
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPW; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     const double* xv[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) xv[v] = X + (v < nv ? v : 0) * ldx;
@@ -1166,11 +1097,7 @@ __global__ __launch_bounds__(kBlock) void gemv_mxres(const double* __restrict__ 
     const int64_t row0 = (wave * G + g) * RPG;
     const double* arow[RPG];
 #pragma unroll
-    for (int r = 0; r < RPG; ++r) {
-        int64_t rr = row0 + r;
-        rr = rr < M ? rr : M - 1;
-        arow[r] = A + rr * lda;
-    }
+    for (int r = 0; r < RPG; ++r) arow[r] = row_ptr(A, lda, row0 + r, M);
     double acc[RPG][NV];
 #pragma unroll
     for (int r = 0; r < RPG; ++r)
@@ -1276,43 +1203,129 @@ __global__ __launch_bounds__(kBlock) void gemv_mxres(const double* __restrict__ 
 //            deterministic. The column tail (K % 2T) is summed from global memory.
 // Needs 16-B aligned A and X with even lda and ldx, 16*RQ rows of lda and NV rows of ldx within
 // 32-bit byte offsets (host-checked: dma_ok).
+//
+// The ring itself is shared with gemv_mdma16 (below): tile geometry, A offsets, issue, the ring
+// loop with its waits, and the partials' wave-order sum. The x-slot mapping, consume and the
+// column tail are each kernel's own.
+template <int RQ, int T, int NB, int NV>
+struct DmaTile {
+    static constexpr int kT = T;                       // 16-B chunks per tile row
+    static constexpr int kBufs = NB;                   // ring depth
+    static constexpr int RB = 16 * RQ;                 // rows per workgroup
+    static constexpr int kRows = 64 / T;               // rows one DMA instruction fills (1 KiB)
+    static constexpr int kInst = RB / kRows;           // A instructions per tile
+    static constexpr int kXInst = (NV * T + 63) / 64;  // x instructions per tile
+    static constexpr int kPer = kInst + kXInst;
+    static constexpr int kInFlight = kPer * (NB - 1);
+    static_assert(kInFlight <= 63, "loads in flight must fit the vmcnt counter");
+    static constexpr int kCols = 2 * T;
+    static constexpr int kRowBytes = 16 * T;
+    static constexpr int kTileBytes = RB * kRowBytes;
+    static constexpr int kBufBytes = kTileBytes + kXInst * 1024;
+    static_assert(NB * kBufBytes >= RQ * NV * 16 * (int)sizeof(double), "partials fit the ring");
+};
+
+// A instruction j, lane -> tile row j*kRows + lane/T (rows past M re-read the last row), LDS
+// slot lane%T of that row, which holds the row's chunk slot ^ (row & 15).
+template <class G>
+__device__ __forceinline__ uint32_t dma_a_offset(int j, int lane, int64_t r0, int64_t M, int64_t lda) {
+    constexpr int T = G::kT;
+    const int row = j * G::kRows + lane / T;
+    const int64_t rr = r0 + row < M ? row : M - 1 - r0;
+    return (uint32_t)((rr * lda + 2 * ((lane % T) ^ (row & 15))) * (int64_t)sizeof(double));
+}
+
+// ROT > 0: workgroup b starts at tile b*ROT (mod ntiles) and wraps around, so workgroups in
+// flight read different columns (rows a power-of-two stride apart otherwise hit the same
+// HBM channels at the same time)
+template <int ROT>
+__device__ __forceinline__ int64_t dma_rot(int64_t ntiles) {
+    return ROT > 0 && ntiles > 0 ? ((int64_t)blockIdx.x * ROT) % ntiles : 0;
+}
+
+// Tile t (rotated by rot) of A (nt) and of x into ring buffer buf.
+template <class G>
+__device__ __forceinline__ void dma_issue(unsigned char* buf, const unsigned char* a0, const unsigned char* x0,
+                                          const uint32_t (&aoff)[G::kInst], const uint32_t (&xoff)[G::kXInst],
+                                          int64_t t, int64_t rot, int64_t ntiles) {
+    t += rot;
+    if (t >= ntiles) t -= ntiles;
+    const int64_t colb = t * G::kCols * (int64_t)sizeof(double);
+#pragma unroll
+    for (int j = 0; j < G::kInst; ++j)
+        __builtin_amdgcn_global_load_lds((gbl_void_t)(a0 + colb + aoff[j]), (lds_void_t)(buf + j * 1024), 16, 0,
+                                         2 /* nt */);
+#pragma unroll
+    for (int j = 0; j < G::kXInst; ++j)
+        __builtin_amdgcn_global_load_lds((gbl_void_t)(x0 + colb + xoff[j]),
+                                         (lds_void_t)(buf + G::kTileBytes + j * 1024), 16, 0, 0);
+}
+
+// The NB-deep ring of wave w: tiles w, w + NW, ... of ntiles; NB - 1 tiles in flight behind the
+// one consumed. issue(t, b) starts tile t into buffer b, consume(b) sums buffer b.
+template <class G, int NW, class ISSUE, class CONSUME>
+__device__ __forceinline__ void dma_ring(int w, int64_t ntiles, ISSUE&& issue, CONSUME&& consume) {
+    constexpr int NB = G::kBufs;
+    const int64_t nt = ntiles > w ? (ntiles - w + NW - 1) / NW : 0;  // this wave's tiles
+#pragma unroll
+    for (int p = 0; p < NB - 1; ++p)
+        if (p < nt) issue(w + (int64_t)NW * p, p);
+    for (int64_t u = 0; u < nt; ++u) {
+        const int64_t un = u + NB - 1;
+        if (un < nt) {
+            // buffer un % NB was summed in iteration u-1; its ds_reads have returned (their
+            // values fed the FMAs), the wait only keeps the order explicit
+            wait_lgkmcnt0();
+            issue(w + (int64_t)NW * un, (int)(un % NB));
+            wait_vmcnt<G::kInFlight>();
+        } else {
+            wait_vmcnt<0>();
+        }
+        consume((int)(u % NB));
+    }
+}
+
+// The wave's own ring as room for its partial sums, once all its DMA has retired and its reads
+// are consumed.
+__device__ __forceinline__ double* ring_as_partials(unsigned char* ring) {
+    wait_vmcnt<0>();
+    wait_lgkmcnt0();
+    return reinterpret_cast<double*>(ring);
+}
+
+// Partial t of every wave, added in wave order (fixed, deterministic); after the barrier that
+// follows the partials' stores.
+template <int NW, int BYTES>
+__device__ __forceinline__ double ring_partial_sum(const unsigned char (&lds)[NW][BYTES], int t) {
+    double s = 0.0;
+#pragma unroll
+    for (int ww = 0; ww < NW; ++ww) s += reinterpret_cast<const double*>(lds[ww])[t];
+    return s;
+}
+
 template <int RQ, int T, int NB, int NW, int NV, int ROT>
 __global__ __launch_bounds__(NW * 64) void gemv_mdma(const double* __restrict__ A, int64_t lda,
                                                      const double* __restrict__ X, int64_t ldx,
                                                      double* __restrict__ Y, int64_t ldy, int64_t M,
                                                      int64_t K, int nv) {
     static_assert(T == 16 || T == 32 || T == 64, "tile width: 16, 32 or 64 chunks of 16 B");
-    constexpr int RB = 16 * RQ;                   // rows per workgroup
-    constexpr int kRows = 64 / T;                 // rows one DMA instruction fills (1 KiB)
-    constexpr int kInst = RB / kRows;             // A instructions per tile
-    constexpr int kXInst = (NV * T + 63) / 64;    // x instructions per tile
-    constexpr int kPer = kInst + kXInst;
-    static_assert(kPer * (NB - 1) <= 63, "loads in flight must fit the vmcnt counter");
-    constexpr int kCols = 2 * T;
-    constexpr int kRowBytes = 16 * T;
-    constexpr int kTileBytes = RB * kRowBytes;
-    constexpr int kBufBytes = kTileBytes + kXInst * 1024;
-    static_assert(NB * kBufBytes >= RQ * NV * 16 * (int)sizeof(double), "partials fit the ring");
+    using G = DmaTile<RQ, T, NB, NV>;
+    constexpr int kRowBytes = G::kRowBytes, kTileBytes = G::kTileBytes, kBufBytes = G::kBufBytes;
     __shared__ __attribute__((aligned(16))) unsigned char lds[NW][NB * kBufBytes];
 
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * RB;
-    const int64_t ntiles = K / kCols;
+    const int64_t r0 = (int64_t)blockIdx.x * G::RB;
+    const int64_t ntiles = K / G::kCols;
     unsigned char* const ring = lds[w];
 
-    // DMA side: A instruction j, lane -> tile row j*kRows + lane/T (rows past M re-read the
-    // last row), LDS slot lane%T; x instruction j, lane -> flat [v][chunk] index 64j + lane
+    // DMA side: A by dma_a_offset; x instruction j, lane -> flat [v][chunk] index 64j + lane
     // (vectors past nv re-read vector 0, indices past NV*T land in the padding).
-    uint32_t aoff[kInst], xoff[kXInst];
+    uint32_t aoff[G::kInst], xoff[G::kXInst];
 #pragma unroll
-    for (int j = 0; j < kInst; ++j) {
-        const int row = j * kRows + lane / T;
-        const int64_t rr = r0 + row < M ? row : M - 1 - r0;
-        aoff[j] = (uint32_t)((rr * lda + 2 * ((lane % T) ^ (row & 15))) * (int64_t)sizeof(double));
-    }
+    for (int j = 0; j < G::kInst; ++j) aoff[j] = dma_a_offset<G>(j, lane, r0, M, lda);
 #pragma unroll
-    for (int j = 0; j < kXInst; ++j) {
+    for (int j = 0; j < G::kXInst; ++j) {
         int q = 64 * j + lane;
         q = q < NV * T ? q : NV * T - 1;
         const int v = q / T;
@@ -1320,24 +1333,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma(const double* __restrict__ 
     }
     const unsigned char* const a0 = reinterpret_cast<const unsigned char*>(A + r0 * lda);
     const unsigned char* const x0 = reinterpret_cast<const unsigned char*>(X);
-    // ROT > 0: workgroup b starts at tile b*ROT (mod ntiles) and wraps around, so workgroups in
-    // flight read different columns (rows a power-of-two stride apart otherwise hit the same
-    // HBM channels at the same time)
-    const int64_t rot = ROT > 0 && ntiles > 0 ? ((int64_t)blockIdx.x * ROT) % ntiles : 0;
-    auto issue = [&](int64_t t, int b) {
-        t += rot;
-        if (t >= ntiles) t -= ntiles;
-        const int64_t colb = t * kCols * (int64_t)sizeof(double);
-        unsigned char* buf = ring + b * kBufBytes;
-#pragma unroll
-        for (int j = 0; j < kInst; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void_t)(a0 + colb + aoff[j]), (lds_void_t)(buf + j * 1024),
-                                             16, 0, 2 /* nt */);
-#pragma unroll
-        for (int j = 0; j < kXInst; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void_t)(x0 + colb + xoff[j]),
-                                             (lds_void_t)(buf + kTileBytes + j * 1024), 16, 0, 0);
-    };
+    const int64_t rot = dma_rot<ROT>(ntiles);
+    auto issue = [&](int64_t t, int b) { dma_issue<G>(ring + b * kBufBytes, a0, x0, aoff, xoff, t, rot, ntiles); };
 
     const int i = lane & 15;
     const int g = lane >> 4;
@@ -1368,26 +1365,10 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma(const double* __restrict__ 
         }
     };
 
-    const int64_t nt = ntiles > w ? (ntiles - w + NW - 1) / NW : 0;  // this wave's tiles
-#pragma unroll
-    for (int p = 0; p < NB - 1; ++p)
-        if (p < nt) issue(w + (int64_t)NW * p, p);
-    for (int64_t u = 0; u < nt; ++u) {
-        const int64_t un = u + NB - 1;
-        if (un < nt) {
-            // buffer un % NB was summed in iteration u-1; its ds_reads have returned (their
-            // values fed the FMAs), the wait only keeps the order explicit
-            wait_lgkmcnt0();
-            issue(w + (int64_t)NW * un, (int)(un % NB));
-            wait_vmcnt<kPer*(NB - 1)>();
-        } else {
-            wait_vmcnt<0>();
-        }
-        consume((int)(u % NB));
-    }
+    dma_ring<G, NW>(w, ntiles, issue, consume);
 
     // column tail: column c of rows i + 16q, columns spread over the waves and the four g lanes
-    for (int64_t c = ntiles * kCols + 4 * w + g; c < K; c += 4 * NW) {
+    for (int64_t c = ntiles * G::kCols + 4 * w + g; c < K; c += 4 * NW) {
 #pragma unroll
         for (int q = 0; q < RQ; ++q) {
             const int64_t rr = r0 + i + 16 * q < M ? r0 + i + 16 * q : M - 1;
@@ -1411,10 +1392,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma(const double* __restrict__ 
             for (int v = 0; v < NV; ++v)
                 if (g == 0 && r0 + i + 16 * q < M && v < nv) Y[v * ldy + r0 + i + 16 * q] = acc[q][v];
     } else {
-        // partials [q][v][i] in the wave's own ring (all its DMA retired and its reads consumed)
-        wait_vmcnt<0>();
-        wait_lgkmcnt0();
-        double* part = reinterpret_cast<double*>(ring);
+        // partials [q][v][i] in the wave's own ring
+        double* part = ring_as_partials(ring);
         if (g == 0) {
 #pragma unroll
             for (int q = 0; q < RQ; ++q)
@@ -1425,12 +1404,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma(const double* __restrict__ 
         for (int t = threadIdx.x; t < RQ * NV * 16; t += NW * 64) {
             const int ii = t % 16, v = (t / 16) % NV, q = t / (16 * NV);
             const int64_t row = r0 + ii + 16 * q;
-            if (row < M && v < nv) {
-                double s = 0.0;
-#pragma unroll
-                for (int ww = 0; ww < NW; ++ww) s += reinterpret_cast<const double*>(lds[ww])[t];
-                Y[v * ldy + row] = s;
-            }
+            if (row < M && v < nv) Y[v * ldy + row] = ring_partial_sum<NW>(lds, t);
         }
     }
 }
@@ -1457,35 +1431,21 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma16(const double* __restrict_
                                                        double* __restrict__ Y, int64_t ldy, int64_t M,
                                                        int64_t K, int nv) {
     static_assert(T == 16 || T == 32, "tile width: 16 or 32 chunks of 16 B");
-    constexpr int NV = 16;
-    constexpr int RB = 16 * RQ;
-    constexpr int kRows = 64 / T;
-    constexpr int kInst = RB / kRows;
-    constexpr int kXInst = NV * T / 64;
-    constexpr int kPer = kInst + kXInst;
-    static_assert(kPer * (NB - 1) <= 63, "loads in flight must fit the vmcnt counter");
-    constexpr int kCols = 2 * T;
-    constexpr int kRowBytes = 16 * T;
-    constexpr int kTileBytes = RB * kRowBytes;
-    constexpr int kBufBytes = kTileBytes + kXInst * 1024;
-    static_assert(NB * kBufBytes >= RQ * 4 * 64 * (int)sizeof(double), "partials fit the ring");
+    using G = DmaTile<RQ, T, NB, 16>;  // the partials (4 registers x 64 lanes per row group) fit as 16 x 16
+    constexpr int kRowBytes = G::kRowBytes, kTileBytes = G::kTileBytes, kBufBytes = G::kBufBytes;
     __shared__ __attribute__((aligned(16))) unsigned char lds[NW][NB * kBufBytes];
 
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * RB;
-    const int64_t ntiles = K / kCols;
+    const int64_t r0 = (int64_t)blockIdx.x * G::RB;
+    const int64_t ntiles = K / G::kCols;
     unsigned char* const ring = lds[w];
 
-    uint32_t aoff[kInst], xoff[kXInst];
+    uint32_t aoff[G::kInst], xoff[G::kXInst];
 #pragma unroll
-    for (int j = 0; j < kInst; ++j) {
-        const int row = j * kRows + lane / T;
-        const int64_t rr = r0 + row < M ? row : M - 1 - r0;
-        aoff[j] = (uint32_t)((rr * lda + 2 * ((lane % T) ^ (row & 15))) * (int64_t)sizeof(double));
-    }
+    for (int j = 0; j < G::kInst; ++j) aoff[j] = dma_a_offset<G>(j, lane, r0, M, lda);
 #pragma unroll
-    for (int j = 0; j < kXInst; ++j) {
+    for (int j = 0; j < G::kXInst; ++j) {
         const int q = 64 * j + lane;  // LDS slot: vector q / T, slot q % T
         const int v = q / T;
         const int c = (q % T) ^ (v & 15);
@@ -1493,21 +1453,8 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma16(const double* __restrict_
     }
     const unsigned char* const a0 = reinterpret_cast<const unsigned char*>(A + r0 * lda);
     const unsigned char* const x0 = reinterpret_cast<const unsigned char*>(X);
-    const int64_t rot = ROT > 0 && ntiles > 0 ? ((int64_t)blockIdx.x * ROT) % ntiles : 0;
-    auto issue = [&](int64_t t, int b) {
-        t += rot;
-        if (t >= ntiles) t -= ntiles;
-        const int64_t colb = t * kCols * (int64_t)sizeof(double);
-        unsigned char* buf = ring + b * kBufBytes;
-#pragma unroll
-        for (int j = 0; j < kInst; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void_t)(a0 + colb + aoff[j]), (lds_void_t)(buf + j * 1024),
-                                             16, 0, 2 /* nt */);
-#pragma unroll
-        for (int j = 0; j < kXInst; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void_t)(x0 + colb + xoff[j]),
-                                             (lds_void_t)(buf + kTileBytes + j * 1024), 16, 0, 0);
-    };
+    const int64_t rot = dma_rot<ROT>(ntiles);
+    auto issue = [&](int64_t t, int b) { dma_issue<G>(ring + b * kBufBytes, a0, x0, aoff, xoff, t, rot, ntiles); };
 
     const int i = lane & 15;  // A row / x vector of this lane's operands
     const int g = lane >> 4;  // k index
@@ -1530,26 +1477,12 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma16(const double* __restrict_
         }
     };
 
-    const int64_t nt = ntiles > w ? (ntiles - w + NW - 1) / NW : 0;
-#pragma unroll
-    for (int p = 0; p < NB - 1; ++p)
-        if (p < nt) issue(w + (int64_t)NW * p, p);
-    for (int64_t u = 0; u < nt; ++u) {
-        const int64_t un = u + NB - 1;
-        if (un < nt) {
-            wait_lgkmcnt0();
-            issue(w + (int64_t)NW * un, (int)(un % NB));
-            wait_vmcnt<kPer*(NB - 1)>();
-        } else {
-            wait_vmcnt<0>();
-        }
-        consume((int)(u % NB));
-    }
+    dma_ring<G, NW>(w, ntiles, issue, consume);
 
     // column tail through the same MFMAs: 4 columns a step (k index g), zero past K
     {
         const double* xj = X + (i < nv ? i : 0) * ldx;
-        for (int64_t c0 = ntiles * kCols + 4 * w; c0 < K; c0 += 4 * NW) {
+        for (int64_t c0 = ntiles * G::kCols + 4 * w; c0 < K; c0 += 4 * NW) {
             const int64_t c = c0 + g;
             const double xv = c < K ? xj[c] : 0.0;
 #pragma unroll
@@ -1571,9 +1504,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma16(const double* __restrict_
                 if (row < M && i < nv) Y[i * ldy + row] = acc[q][r];
             }
     } else {
-        wait_vmcnt<0>();
-        wait_lgkmcnt0();
-        double* part = reinterpret_cast<double*>(ring);
+        double* part = ring_as_partials(ring);
 #pragma unroll
         for (int q = 0; q < RQ; ++q)
 #pragma unroll
@@ -1582,12 +1513,7 @@ __global__ __launch_bounds__(NW * 64) void gemv_mdma16(const double* __restrict_
         for (int t = threadIdx.x; t < RQ * 4 * 64; t += NW * 64) {
             const int l = t % 64, r = (t / 64) % 4, q = t / 256;
             const int64_t row = r0 + 16 * q + (l >> 4) + 4 * r;
-            if (row < M && (l & 15) < nv) {
-                double s = 0.0;
-#pragma unroll
-                for (int ww = 0; ww < NW; ++ww) s += reinterpret_cast<const double*>(lds[ww])[t];
-                Y[(l & 15) * ldy + row] = s;
-            }
+            if (row < M && (l & 15) < nv) Y[(l & 15) * ldy + row] = ring_partial_sum<NW>(lds, t);
         }
     }
 }

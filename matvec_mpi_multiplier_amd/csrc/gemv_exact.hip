@@ -309,6 +309,50 @@ __device__ __forceinline__ double hop_masked_segment(double sum, const double* _
     return fwd ? hop_segment<L, W, true>(sum, ta, tx) : hop_segment<L, W, false>(sum, ta, tx);
 }
 
+// The chain over nseg whole segments, shared by the hop kernels: U slots of a segment's A and x
+// each. load_a(g, i, a) / load_x(g, i, xv) load segment g into slot i; slot 0's segment runs
+// forward when FWD0, and the directions alternate from there (U is even, so slot i always has
+// the direction of its parity).
+//   prime : slots 0 .. U-1 take segments 0 .. U-1 (the last one again past nseg);
+//   groups: whole groups of U segments, one basic block: slot i is summed, then refilled U
+//           segments ahead; the scheduling barriers keep the loads in slot order, so the
+//           compiler's vmcnt waits retire exactly the slot about to be summed
+//           (strict <: a group whose refills would all lie past the row's last segment is left
+//           to the drain instead of re-reading that segment U times);
+//   drain : the last nseg - base <= U segments are already in slots 0 .. nseg - base - 1.
+template <int L, int W, int U, bool FWD0, class LOADA, class LOADX>
+__device__ __forceinline__ double hop_chain(double sum, int64_t nseg, LOADA&& load_a, LOADX&& load_x) {
+    static_assert(U % 2 == 0, "slot i keeps the direction of its parity across groups");
+    constexpr int V = W / 2;
+    if (nseg > 0) {
+        dbl2x a[U][V], xv[U][V];
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const int64_t sg = i < nseg ? i : nseg - 1;
+            load_a(sg, i, a[i]);
+            load_x(sg, i, xv[i]);
+            __builtin_amdgcn_sched_barrier(0);  // same load order as the loop's refills
+        }
+        int64_t base = 0;
+        for (; base + U < nseg; base += U) {
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                sum = (i & 1) ? hop_segment<L, W, !FWD0>(sum, a[i], xv[i]) : hop_segment<L, W, FWD0>(sum, a[i], xv[i]);
+                __builtin_amdgcn_sched_barrier(0);
+                const int64_t sg = base + i + U < nseg ? base + i + U : nseg - 1;
+                load_a(sg, i, a[i]);
+                load_x(sg, i, xv[i]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < U; ++i)
+            if (base + i < nseg)
+                sum = (i & 1) ? hop_segment<L, W, !FWD0>(sum, a[i], xv[i]) : hop_segment<L, W, FWD0>(sum, a[i], xv[i]);
+    }
+    return sum;
+}
+
 // every row of A starts on a 128-B line: A on a line and lda a multiple of 16 doubles
 __device__ __forceinline__ bool lines_aligned(const double* A, int64_t lda) {
     return (((uintptr_t)A & 127u) == 0) && (lda % 16 == 0);
@@ -352,39 +396,11 @@ __global__ __launch_bounds__(64 * NW) void gemv_seq_hop(const double* __restrict
         ntail = (K - nseg * S + S - 1) / S;            // what any row has left: 0, 1 or 2 segments (0: line-aligned rows of whole segments)
         const double* ar = arow + h;
         const double* xr = x + h;
-        if (nseg > 0) {
-            dbl2x a[U][V], xv[U][V];
-#pragma unroll
-            for (int i = 0; i < U; ++i) {
-                const int64_t sg = i < nseg ? i : nseg - 1;
-                load_run<V, B8, true>(ar + sg * S + off[(i + 1) & 1], a[i]);
-                load_run<V, true, false>(xr + sg * S + off[(i + 1) & 1], xv[i]);
-                __builtin_amdgcn_sched_barrier(0);  // same load order as the loop's refills
-            }
-            // Whole groups of U segments, one basic block: slot i is summed, then refilled U
-            // segments ahead; the scheduling barriers keep the loads in slot order, so the
-            // compiler's vmcnt waits retire exactly the slot about to be summed. Main segment i
-            // is the row's segment i + 1 (after the head).
-            // (strict <: a group whose refills would all lie past the row's last segment is left
-            // to the remainder below instead of re-reading that segment U times)
-            int64_t base = 0;
-            for (; base + U < nseg; base += U) {
-#pragma unroll
-                for (int i = 0; i < U; ++i) {
-                    sum = (i & 1) ? hop_segment<L, W, true>(sum, a[i], xv[i]) : hop_segment<L, W, false>(sum, a[i], xv[i]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int64_t sg = base + i + U < nseg ? base + i + U : nseg - 1;
-                    load_run<V, B8, true>(ar + sg * S + off[(i + 1) & 1], a[i]);
-                    load_run<V, true, false>(xr + sg * S + off[(i + 1) & 1], xv[i]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            // the last nseg - base <= U segments are already in slots 0 .. nseg - base - 1 (base is even)
-#pragma unroll
-            for (int i = 0; i < U; ++i)
-                if (base + i < nseg)
-                    sum = (i & 1) ? hop_segment<L, W, true>(sum, a[i], xv[i]) : hop_segment<L, W, false>(sum, a[i], xv[i]);
-        }
+        // main segment sg is the row's segment sg + 1 (after the head): slot 0 runs backwards
+        sum = hop_chain<L, W, U, false>(
+            sum, nseg,
+            [&](int64_t sg, int i, dbl2x (&d)[V]) { load_run<V, B8, true>(ar + sg * S + off[(i + 1) & 1], d); },
+            [&](int64_t sg, int i, dbl2x (&d)[V]) { load_run<V, true, false>(xr + sg * S + off[(i + 1) & 1], d); });
         for (int64_t t = 0; t < ntail; ++t) {
             const int64_t g = 1 + nseg + t;  // the row's segment index
             sum = hop_masked_segment<L, W>(sum, arow, x, h + (nseg + t) * S + off[g & 1], h, K, (g & 1) == 0);
@@ -427,36 +443,14 @@ __global__ __launch_bounds__(64 * NW) void gemv_seq_hop_xl(const double* __restr
         ntail = (K - nseg * S + S - 1) / S;  // 0, 1 or 2 tail segments, as in gemv_seq_hop
         const double* ar = arow + h;
         const double* xr = xl + h;
-        auto xload = [&](const double* p, dbl2x (&d)[V]) {
+        sum = hop_chain<L, W, U, false>(
+            sum, nseg,
+            [&](int64_t sg, int i, dbl2x (&d)[V]) { load_run<V, true, true>(ar + sg * S + off[(i + 1) & 1], d); },
+            [&](int64_t sg, int i, dbl2x (&d)[V]) {  // x from LDS
+                const double* p = xr + sg * S + off[(i + 1) & 1];
 #pragma unroll
-            for (int v = 0; v < V; ++v) d[v] = dbl2x{p[2 * v], p[2 * v + 1]};
-        };
-        if (nseg > 0) {
-            dbl2x a[U][V], xv[U][V];
-#pragma unroll
-            for (int i = 0; i < U; ++i) {
-                const int64_t sg = i < nseg ? i : nseg - 1;
-                load_run<V, true, true>(ar + sg * S + off[(i + 1) & 1], a[i]);
-                xload(xr + sg * S + off[(i + 1) & 1], xv[i]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            int64_t base = 0;
-            for (; base + U < nseg; base += U) {
-#pragma unroll
-                for (int i = 0; i < U; ++i) {
-                    sum = (i & 1) ? hop_segment<L, W, true>(sum, a[i], xv[i]) : hop_segment<L, W, false>(sum, a[i], xv[i]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int64_t sg = base + i + U < nseg ? base + i + U : nseg - 1;
-                    load_run<V, true, true>(ar + sg * S + off[(i + 1) & 1], a[i]);
-                    xload(xr + sg * S + off[(i + 1) & 1], xv[i]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < U; ++i)
-                if (base + i < nseg)
-                    sum = (i & 1) ? hop_segment<L, W, true>(sum, a[i], xv[i]) : hop_segment<L, W, false>(sum, a[i], xv[i]);
-        }
+                for (int v = 0; v < V; ++v) d[v] = dbl2x{p[2 * v], p[2 * v + 1]};
+            });
         for (int64_t t = 0; t < ntail; ++t) {
             const int64_t g = 1 + nseg + t;
             sum = hop_masked_segment<L, W>(sum, arow, x, h + (nseg + t) * S + off[g & 1], h, K, (g & 1) == 0);
@@ -504,36 +498,10 @@ __global__ __launch_bounds__(64) void gemv_seq_hop_panel(const double* __restric
     auto seg = [&](int64_t g) { return arow + ((g * S) >> lp) * pstride + ((g * S) & pmask); };
     const int64_t nseg = K / S;
     const int64_t tail = K - nseg * S;
-    double sum = 0.0;
-    if (nseg > 0) {
-        dbl2x a[U][V], xv[U][V];
-#pragma unroll
-        for (int i = 0; i < U; ++i) {
-            const int64_t g = i < nseg ? i : nseg - 1;
-            load_run<V, false, true>(seg(g) + off[i & 1], a[i]);
-            load_run<V, false, false>(x + g * S + off[i & 1], xv[i]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // as in gemv_seq_hop: slot i is summed, then refilled U segments ahead, loads kept in
-        // slot order so the counted vmcnt waits retire exactly the slot about to be summed;
-        // segment g runs forward when g is even (base is a multiple of U, U even)
-        int64_t base = 0;
-        for (; base + U < nseg; base += U) {
-#pragma unroll
-            for (int i = 0; i < U; ++i) {
-                sum = (i & 1) ? hop_segment<L, W, false>(sum, a[i], xv[i]) : hop_segment<L, W, true>(sum, a[i], xv[i]);
-                __builtin_amdgcn_sched_barrier(0);
-                const int64_t g = base + i + U < nseg ? base + i + U : nseg - 1;
-                load_run<V, false, true>(seg(g) + off[i & 1], a[i]);
-                load_run<V, false, false>(x + g * S + off[i & 1], xv[i]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < U; ++i)
-            if (base + i < nseg)
-                sum = (i & 1) ? hop_segment<L, W, false>(sum, a[i], xv[i]) : hop_segment<L, W, true>(sum, a[i], xv[i]);
-    }
+    // no head: segment g runs forward when g is even, slot 0 forward (hop_chain)
+    double sum = hop_chain<L, W, U, true>(
+        0.0, nseg, [&](int64_t g, int i, dbl2x (&d)[V]) { load_run<V, false, true>(seg(g) + off[i & 1], d); },
+        [&](int64_t g, int i, dbl2x (&d)[V]) { load_run<V, false, false>(x + g * S + off[i & 1], d); });
     if (tail > 0) {
         // the last K % S columns: a masked segment over the panel's columns (zeros outside K);
         // hop_masked_segment indexes by column, so hand it the segment's base shifted back by gS
@@ -733,23 +701,15 @@ static bool operands_ok(int needs, int64_t lda, bool aligned) {
     return needs == kVec16 || lda < (1ll << 23);
 }
 
-template <typename T, size_t N>
-constexpr int seq_id(const T (&table)[N], const char* name) {
-    for (size_t i = 0; i < N; ++i) {
-        const char *a = table[i].name, *b = name;
-        while (*a && *a == *b) ++a, ++b;
-        if (*a == *b) return (int)i;
-    }
-    return -1;
-}
-constexpr int kSeqScalar = seq_id(kSeqVariants, "seq_scalar");
-constexpr int kSeqManyRows = seq_id(kSeqVariants, "seqx_r64_t16_b2_g8");
-constexpr int kHopRows = seq_id(kSeqVariants, "hop8_l8_w2_u16");
-constexpr int kHopLongRows = seq_id(kSeqVariants, "hop8_l8_w2_u24");
-constexpr int kHopWide = seq_id(kSeqVariants, "hop8_l16_w4_u8");
-constexpr int kHopWidest = seq_id(kSeqVariants, "hop8_l16_w8_u4");
-constexpr int kHopFewRows = seq_id(kSeqVariants, "hop8_l32_w8_u4");
-constexpr int kHopEven = seq_id(kSeqVariants, "hop8e_l8_w2_u16_n8");
+// the dispatch's picks, by name (variant_id, common.h)
+constexpr int kSeqScalar = variant_id(kSeqVariants, "seq_scalar");
+constexpr int kSeqManyRows = variant_id(kSeqVariants, "seqx_r64_t16_b2_g8");
+constexpr int kHopRows = variant_id(kSeqVariants, "hop8_l8_w2_u16");
+constexpr int kHopLongRows = variant_id(kSeqVariants, "hop8_l8_w2_u24");
+constexpr int kHopWide = variant_id(kSeqVariants, "hop8_l16_w4_u8");
+constexpr int kHopWidest = variant_id(kSeqVariants, "hop8_l16_w8_u4");
+constexpr int kHopFewRows = variant_id(kSeqVariants, "hop8_l32_w8_u4");
+constexpr int kHopEven = variant_id(kSeqVariants, "hop8e_l8_w2_u16_n8");
 static_assert(kHopEven > 0 && kSeqVariants[kHopEven].needs == kAnyOperands, "the evenly placed pick takes any operands");
 static_assert(kSeqScalar > 0 && kSeqVariants[kSeqScalar].needs == kAnyOperands, "8-B exact fallback");
 static_assert(kSeqManyRows > 0 && kHopRows > 0 && kHopLongRows > 0 && kHopWide > 0 && kHopWidest > 0 &&
@@ -776,8 +736,6 @@ static_assert(kSeqVariants[kHopRows].needs == kAnyOperands && kSeqVariants[kHopL
 // config 5's shards and 4,194,304 x 512 run at 0.96-1.0 of the tree form's speed.
 // short rows (K <= 768) go out in launches of at most 1 GiB of A (mvg_gemv_exact_variant below)
 constexpr int64_t kShortRowK = 768;
-constexpr int64_t kShortRowLaunchBytes = 1ll << 30;
-constexpr int64_t kMinPieceRows = 65536;
 constexpr int kMi355xCUs = 256;  // when no device answers (host-only callers, tests)
 //
 // Evenly placed 8-lane forms (round 4, profiles/r04/r4g, r4h): the 8-lane hop forms' one-wave
@@ -883,7 +841,7 @@ static constexpr PanelVariant kPanelVariants[] = {
 };
 #undef PANEL
 constexpr int kNumPanelVariants = (int)(sizeof(kPanelVariants) / sizeof(kPanelVariants[0]));
-constexpr int kPanelRows = seq_id(kPanelVariants, "panel_l8_w2_u8");
+constexpr int kPanelRows = variant_id(kPanelVariants, "panel_l8_w2_u8");
 static_assert(kPanelRows > 0, "panel dispatch names a missing variant");
 constexpr int64_t kPanelWidth = 256;
 
@@ -940,12 +898,9 @@ int mvg_gemv_exact_variant(const double* A, int64_t lda, const double* x, double
     // short rows (K <= 768): at most 1 GiB of A per launch, as the tree form's one-row waves
     // (gemv.hip): config 5's 16 GiB in 2.46 ms instead of 2.58, its 2 GiB shard 316 against
     // 318 us (round 3, profiles/r03/sublaunch/)
-    // (1 GiB of the bytes read, k per row, never under 65536 rows: a view's wider lda does not
-    // shrink the pieces below what fills the chip)
+    // (the cap: short_row_piece_rows, common.h)
     if (k > 0 && k <= kShortRowK) {
-        int64_t cap = kShortRowLaunchBytes / (k * (int64_t)sizeof(double));
-        if (cap < kMinPieceRows) cap = kMinPieceRows;
-        cap = cap / var.rows * var.rows;
+        const int64_t cap = short_row_piece_rows(k, var.rows);
         if (cap < max_rows) max_rows = cap;
     }
     size_t lds = var.xlds ? (size_t)k * sizeof(double) : (size_t)var.lds_reserve;

@@ -336,6 +336,22 @@ def test_host_first_touch_zeroes_the_range_without_numa_info():
     assert _lib.lib.mvg_host_first_touch(small.ctypes.data, small.nbytes, 0) == 0 and not small.any()
 
 
+# variant ids are recorded in the committed sweeps ("vid") and the tools select by id range: the
+# four tables keep their entries, names and order (tests/golden/variant_names.json)
+def test_variant_tables_keep_their_names_and_order():
+    import json
+
+    with open(os.path.join(GOLDEN_DIR, "variant_names.json")) as f:
+        golden = json.load(f)
+    assert sorted(golden) == ["mvg_gemv_exact_panel_variant_name", "mvg_gemv_exact_variant_name",
+                              "mvg_gemv_multi_variant_name", "mvg_gemv_variant_name"]
+    for name_fn, want in golden.items():
+        count = getattr(_lib.lib, name_fn.replace("_name", "_count"))()
+        got = [getattr(_lib.lib, name_fn)(v).decode() for v in range(count)]
+        assert got == want, name_fn
+        assert getattr(_lib.lib, name_fn)(count) == b"invalid"
+
+
 # dispatch is host logic (no GPU needed): the names the auto choice resolves to per shape
 def test_auto_variant_names_match_the_dispatch_table():
     names = {k: _lib.lib.mvg_gemv_variant_name(_lib.lib.mvg_gemv_auto_variant(k, m, k)).decode()
