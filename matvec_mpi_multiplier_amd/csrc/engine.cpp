@@ -46,6 +46,13 @@ int nccl_fail(ncclResult_t r, const char* what) {
         if (_r != ncclSuccess) return nccl_fail(_r, #call);             \
     } while (0)
 
+// a step of this file (an int MVG_* code): leave the calling function with its error
+#define MVG_TRY(call)                                                   \
+    do {                                                                \
+        const int _rc = (call);                                         \
+        if (_rc != MVG_OK) return _rc;                                  \
+    } while (0)
+
 struct LocalRank {
     int rank = 0;
     int device = 0;
@@ -62,7 +69,14 @@ struct mvg_comm {
 namespace {
 
 constexpr int kRing = 8;
+// Root-send staging: a peer's shard goes out in pieces of at most this many doubles (256 MiB).
+// Sender and receiver cut the pieces with the same function (shard_pieces).
+constexpr int64_t kStageElems = (256ll << 20) / (int64_t)sizeof(double);
 
+// One rank's streams, events, buffers and communicators. The handles are plain values and
+// free_shard is the one place that releases them: frees need the shard's device current, and
+// the trace (mvg_debug_trace_exchange) builds Shards whose pointers are stand-in addresses
+// that must never reach hipFree.
 struct Shard {
     mvg_shard plan{};
     int device = 0;
@@ -85,9 +99,8 @@ struct Shard {
     int64_t panelP = 0, pstride = 0;
     bool panels_fresh = false;
     int64_t uses = 0;  // multiplies since dA was last written
-    // local product: y_len (row/block) or R (col) doubles; a ring of kRing buffers when an
-    // exchange follows: multiply n writes dy_parts[n % ring] while earlier exchanges still read
-    // the others
+    // local product: plan.y_len doubles; a ring of kRing buffers when an exchange follows:
+    // multiply n writes dy_parts[n % ring] while earlier exchanges still read the others
     double* dy_parts[kRing] = {};
     hipEvent_t gemv_done[kRing] = {};  // GEMV into dy_parts[b] finished
     hipEvent_t x_done[kRing] = {};     // exchange reading dy_parts[b] finished
@@ -99,9 +112,11 @@ struct Shard {
     bool chunks_pending = false;
     double* dy_row = nullptr;   // block-split row leader: reduced slice (lr doubles)
     double* dy = nullptr;       // rank 0: the full y (R doubles)
-    double* stage[2] = {nullptr, nullptr};  // root: staging for root->peer sends (rank mode)
     double* gbuf = nullptr;     // rank 0, exact mode: every rank's partial, gathered in rank order
-    size_t stage_elems = 0;
+    // root, one process per GPU (root_send_shards): two staging buffers of kStageElems doubles in
+    // one allocation, and the events that order their H2D copies and sends; made on first use
+    double* stage = nullptr;
+    hipEvent_t copied[2] = {}, sent[2] = {}, ready = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
     size_t ev_used = 0;
     hipEvent_t span_t0 = nullptr, span_t1 = nullptr;  // span timing (mvg_engine_kernel_timing(-1))
@@ -142,10 +157,9 @@ struct XOps {
     virtual ncclResult_t group_end() = 0;
     virtual void set_device(int dev) = 0;
     virtual ncclResult_t split(ncclComm_t world, int color, int key, ncclComm_t* out) = 0;
-    virtual ncclResult_t gather(const double* src, double* dst, size_t count, int root, ncclComm_t comm,
-                                hipStream_t st) = 0;
-    virtual ncclResult_t reduce(const double* src, double* dst, size_t count, int root, ncclComm_t comm,
-                                hipStream_t st) = 0;
+    // op: MVG_X_GATHER or MVG_X_REDUCE (fp64 sum) of `count` doubles to `root`
+    virtual ncclResult_t collective(int op, const double* src, double* dst, size_t count, int root, ncclComm_t comm,
+                                    hipStream_t st) = 0;
     virtual int combine(const mvg_engine* e, const Shard& s, hipStream_t st) = 0;
 };
 
@@ -156,13 +170,10 @@ struct DeviceXOps final : XOps {
     ncclResult_t split(ncclComm_t world, int color, int key, ncclComm_t* out) override {
         return ncclCommSplit(world, color, key, out, nullptr);
     }
-    ncclResult_t gather(const double* src, double* dst, size_t count, int root, ncclComm_t comm,
-                        hipStream_t st) override {
-        return ncclGather(src, dst, count, ncclFloat64, root, comm, st);
-    }
-    ncclResult_t reduce(const double* src, double* dst, size_t count, int root, ncclComm_t comm,
-                        hipStream_t st) override {
-        return ncclReduce(src, dst, count, ncclFloat64, ncclSum, root, comm, st);
+    ncclResult_t collective(int op, const double* src, double* dst, size_t count, int root, ncclComm_t comm,
+                            hipStream_t st) override {
+        return op == MVG_X_GATHER ? ncclGather(src, dst, count, ncclFloat64, root, comm, st)
+                                  : ncclReduce(src, dst, count, ncclFloat64, ncclSum, root, comm, st);
     }
     int combine(const mvg_engine* e, const Shard& s, hipStream_t st) override {
         return e->alg == MVG_ALG_COLWISE ? launch_combine_mpich_reduce(s.gbuf, e->nranks, e->R, s.dy, st)
@@ -181,6 +192,39 @@ bool needs_row_buffer(const Shard& s) {
     return need;
 }
 
+// Which exchange buffers a rank keeps, and how many doubles each holds, by MVG_X_BUF_*
+// (-1: the rank keeps none). The engine allocates from this and the trace hands out its
+// stand-in addresses from it, so the two cannot disagree. `exact` is the mode asked for.
+struct XBufLens {
+    int64_t len[4];
+};
+XBufLens exchange_buffers(const mvg_engine& e, const Shard& s, bool exact) {
+    // the planner makes y_len = R for the column split: the partial is a whole y there
+    const int64_t part = s.plan.y_len;
+    XBufLens b;
+    b.len[MVG_X_BUF_PART] = part;
+    b.len[MVG_X_BUF_ROW] = needs_row_buffer(s) ? part : -1;
+    b.len[MVG_X_BUF_Y] = s.rank == 0 ? e.R : -1;
+    // exact mode: every rank's partial in rank order (the row split's gather is already exact)
+    const bool gathers = exact && e.alg != MVG_ALG_ROWWISE && s.rank == 0 && s.nsteps > 0;
+    b.len[MVG_X_BUF_GATHERED] = gathers ? part * e.nranks : -1;
+    return b;
+}
+
+// One ncclGroupStart/End with every local shard's call in it. A failing call still closes the
+// group before the error is reported.
+template <class Call>
+int grouped(std::vector<Shard>& shards, XOps& ops, const char* what, Call call) {
+    MVG_NCCL(ops.group_start());
+    ncclResult_t r = ncclSuccess;
+    for (auto& s : shards)
+        if ((r = call(s)) != ncclSuccess) break;
+    const ncclResult_t r2 = ops.group_end();
+    if (r != ncclSuccess) return nccl_fail(r, what);
+    if (r2 != ncclSuccess) return nccl_fail(r2, (std::string(what) + ": ncclGroupEnd").c_str());
+    return MVG_OK;
+}
+
 // Sub-communicators of the exchange schedule. ncclCommSplit is collective over the world, so
 // every local rank calls it for every split step, inside one group per step.
 int split_steps(std::vector<Shard>& shards, XOps& ops) {
@@ -190,18 +234,12 @@ int split_steps(std::vector<Shard>& shards, XOps& ops) {
             for (auto& s : shards) s.xcomm[k] = s.world;
             continue;
         }
-        ncclResult_t r = ops.group_start();
-        if (r != ncclSuccess) return nccl_fail(r, "ncclGroupStart");
-        for (auto& s : shards) {
+        MVG_TRY(grouped(shards, ops, "ncclCommSplit", [&](Shard& s) {
             ops.set_device(s.device);
             const mvg_xstep& st = s.steps[k];
-            r = ops.split(s.world, st.member ? st.color : NCCL_SPLIT_NOCOLOR, st.key, &s.xcomm[k]);
             s.owns_xcomm[k] = true;
-            if (r != ncclSuccess) break;
-        }
-        const ncclResult_t r2 = ops.group_end();
-        if (r != ncclSuccess) return nccl_fail(r, "ncclCommSplit");
-        if (r2 != ncclSuccess) return nccl_fail(r2, "ncclCommSplit group");
+            return ops.split(s.world, st.member ? st.color : NCCL_SPLIT_NOCOLOR, st.key, &s.xcomm[k]);
+        }));
     }
     return MVG_OK;
 }
@@ -232,61 +270,59 @@ struct DeviceGuard {
     ~DeviceGuard() { (void)hipSetDevice(prev); }
 };
 
+// n doubles of device memory; n <= 0 (an empty shard, a buffer this rank does not keep): none.
 int alloc_doubles(double** p, int64_t n) {
-    if (n <= 0) {
-        *p = nullptr;
-        return MVG_OK;
-    }
-    hipError_t e = hipMalloc((void**)p, (size_t)n * sizeof(double));
-    if (e != hipSuccess) {
-        hip_fail(e, "hipMalloc");
-        return MVG_E_NOMEM;
-    }
-    return MVG_OK;
+    *p = nullptr;
+    if (n <= 0) return MVG_OK;
+    const hipError_t e = hipMalloc((void**)p, (size_t)n * sizeof(double));
+    if (e == hipSuccess) return MVG_OK;
+    *p = nullptr;
+    hip_fail(e, "hipMalloc");
+    return MVG_E_NOMEM;
 }
 
 void free_shard(Shard& s) {
     (void)hipSetDevice(s.device);
-    if (s.stream) (void)hipStreamSynchronize(s.stream);
-    if (s.copy_stream) (void)hipStreamSynchronize(s.copy_stream);
-    if (s.xstream) (void)hipStreamSynchronize(s.xstream);
-    for (double* p : {s.dA, s.dAp, s.dx, s.dy_row, s.dy, s.stage[0], s.stage[1], s.gbuf})
+    for (hipStream_t st : {s.stream, s.copy_stream, s.xstream})
+        if (st) (void)hipStreamSynchronize(st);
+    for (double* p : {s.dA, s.dAp, s.dx, s.dy_row, s.dy, s.stage, s.gbuf})
         if (p) (void)hipFree(p);
+    std::vector<hipEvent_t> events = {s.span_t0, s.span_t1, s.copy_ready, s.copied[0], s.copied[1],
+                                      s.sent[0], s.sent[1],  s.ready};
+    events.insert(events.end(), s.chunk_ev.begin(), s.chunk_ev.end());
     for (int b = 0; b < kRing; ++b) {
         if (s.dy_parts[b]) (void)hipFree(s.dy_parts[b]);
-        if (s.gemv_done[b]) (void)hipEventDestroy(s.gemv_done[b]);
-        if (s.x_done[b]) (void)hipEventDestroy(s.x_done[b]);
+        events.insert(events.end(), {s.gemv_done[b], s.x_done[b]});
     }
-    for (auto& ev : s.ev_pool) {
-        (void)hipEventDestroy(ev.first);
-        (void)hipEventDestroy(ev.second);
-    }
-    for (hipEvent_t ev : s.chunk_ev) (void)hipEventDestroy(ev);
-    if (s.span_t0) (void)hipEventDestroy(s.span_t0);
-    if (s.span_t1) (void)hipEventDestroy(s.span_t1);
-    if (s.copy_ready) (void)hipEventDestroy(s.copy_ready);
-    s.ev_pool.clear();
+    for (auto& pair : s.ev_pool) events.insert(events.end(), {pair.first, pair.second});
+    for (hipEvent_t ev : events)
+        if (ev) (void)hipEventDestroy(ev);
     for (int k = 0; k < MVG_MAX_XSTEPS; ++k)
         if (s.owns_xcomm[k] && s.xcomm[k]) (void)ncclCommDestroy(s.xcomm[k]);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
-    if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
-    if (s.xstream) (void)hipStreamDestroy(s.xstream);
+    for (hipStream_t st : {s.stream, s.copy_stream, s.xstream})
+        if (st) (void)hipStreamDestroy(st);
     s = Shard{};
 }
 
 // 2-D host -> device copy of a shard region into a packed device buffer (pitch = cols).
-int h2d_region(double* dst, const double* host, int64_t ld_host, int64_t rows, int64_t cols,
-               hipStream_t s) {
+int h2d_region(double* dst, const double* host, int64_t ld_host, int64_t rows, int64_t cols, hipStream_t s) {
     if (rows == 0 || cols == 0) return MVG_OK;
-    if (cols == ld_host) {
-        MVG_HIP(hipMemcpyAsync(dst, host, (size_t)(rows * cols) * sizeof(double),
-                               hipMemcpyHostToDevice, s));
-    } else {
-        MVG_HIP(hipMemcpy2DAsync(dst, (size_t)cols * sizeof(double), host,
-                                 (size_t)ld_host * sizeof(double), (size_t)cols * sizeof(double),
-                                 (size_t)rows, hipMemcpyHostToDevice, s));
-    }
+    const size_t row_bytes = (size_t)cols * sizeof(double);
+    if (cols == ld_host)
+        MVG_HIP(hipMemcpyAsync(dst, host, (size_t)rows * row_bytes, hipMemcpyHostToDevice, s));
+    else
+        MVG_HIP(hipMemcpy2DAsync(dst, row_bytes, host, (size_t)ld_host * sizeof(double), row_bytes, (size_t)rows,
+                                 hipMemcpyHostToDevice, s));
     return MVG_OK;
+}
+
+// The x segment of a shard (full x for the row split, the strip's or block's columns
+// otherwise) and rows [r0, r0 + rows) of its A, from the host's whole x and A to `dst` on `st`.
+int h2d_x(double* dst, const mvg_shard& p, const double* x, hipStream_t st) {
+    return h2d_region(dst, x + p.col_off, p.n_cols, 1, p.n_cols, st);
+}
+int h2d_rows(double* dst, const mvg_shard& p, const double* A, int64_t r0, int64_t rows, hipStream_t st) {
+    return h2d_region(dst, A + (p.row_off + r0) * p.C + p.col_off, p.C, rows, p.n_cols, st);
 }
 
 // A chunked distribution's copies into dA / dx may still be running on the copy stream. Any
@@ -302,84 +338,150 @@ int drain_chunks(Shard& s) {
     return MVG_OK;
 }
 
-// x segment that a shard needs: full x (row), strip segment (col), block column segment.
-inline int64_t x_off(const mvg_shard& p) { return p.col_off; }
-inline int64_t x_len(const mvg_shard& p) { return p.n_cols; }
+// An untimed event of a shard, made when first needed; free_shard releases it.
+int ensure_event(hipEvent_t* ev) {
+    if (!*ev) MVG_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return MVG_OK;
+}
+
+// Every shard-writing entry point starts here: the panel copies of A are stale, and a write
+// while a kernel-timing span is open would land on the GEMV stream between the span's events,
+// so the span no longer times GEMVs alone.
+bool span_is_open(const mvg_engine* e) { return e->timing_every == -1 && e->span_multiplies > 0; }
+void begin_write(mvg_engine* e) {
+    if (span_is_open(e)) e->span_valid = false;
+    for (auto& s : e->shards) s.panels_fresh = false, s.uses = 0;
+}
+
+// One shard's rows in `nch` chunks on the copy stream, each followed by an event; the next
+// multiply runs each chunk's GEMV as soon as the chunk has landed: only
+// the last chunk's GEMV is left after the transfer.
+int distribute_chunked(Shard& s, const double* A, const double* x, int nch) {
+    MVG_TRY(ensure_event(&s.copy_ready));
+    if ((int)s.chunk_ev.size() < nch) s.chunk_ev.resize(nch, nullptr);
+    // the copies overwrite dA and dx, which the GEMV last queued on s.stream still reads
+    MVG_HIP(hipEventRecord(s.copy_ready, s.stream));
+    MVG_HIP(hipStreamWaitEvent(s.copy_stream, s.copy_ready, 0));
+    MVG_TRY(h2d_x(s.dx, s.plan, x, s.copy_stream));
+    s.chunk_row.assign(nch + 1, 0);
+    for (int c = 0; c <= nch; ++c) s.chunk_row[c] = s.plan.n_rows * c / nch;
+    for (int c = 0; c < nch; ++c) {
+        const int64_t r0 = s.chunk_row[c];
+        MVG_TRY(h2d_rows(s.dA + r0 * s.plan.n_cols, s.plan, A, r0, s.chunk_row[c + 1] - r0, s.copy_stream));
+        MVG_TRY(ensure_event(&s.chunk_ev[c]));
+        MVG_HIP(hipEventRecord(s.chunk_ev[c], s.copy_stream));
+    }
+    s.chunks_pending = true;
+    return MVG_OK;
+}
 
 // Every local device pulls its own shard (and x segment) from host memory that holds the
-// whole A and x, over its own PCIe link, concurrently (one stream per device). With
-// overlap_chunks > 1 the shard's rows go over in that many chunks on the copy stream, each
-// followed by an event, and the next multiply runs each chunk's GEMV as soon as the chunk has
-// landed: only the last chunk's GEMV is left after the transfer.
+// whole A and x, over its own PCIe link, concurrently (one stream per device); in row chunks
+// on the copy stream with overlap_chunks > 1. The whole of mvg_engine_distribute_shared, and of
+// mvg_engine_distribute when all ranks are in this process.
 int distribute_direct(mvg_engine* e, const double* A, const double* x) {
-    const int64_t C = e->C;
+    begin_write(e);
+    DeviceGuard g;
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
-        const mvg_shard& p = s.plan;
-        const int nch = e->overlap_chunks > 1 && p.n_rows >= 2 * (int64_t)e->overlap_chunks ? e->overlap_chunks : 0;
-        if (int rc0 = drain_chunks(s); rc0 != MVG_OK) return rc0;
-        if (nch == 0) {
-            int rc = h2d_region(s.dA, A + p.row_off * C + p.col_off, C, p.n_rows, p.n_cols, s.stream);
-            if (rc != MVG_OK) return rc;
-            rc = h2d_region(s.dx, x + x_off(p), x_len(p), 1, x_len(p), s.stream);
-            if (rc != MVG_OK) return rc;
-            continue;
+        MVG_TRY(drain_chunks(s));
+        if (e->overlap_chunks > 1 && s.plan.n_rows >= 2 * (int64_t)e->overlap_chunks) {
+            MVG_TRY(distribute_chunked(s, A, x, e->overlap_chunks));
+        } else {
+            MVG_TRY(h2d_rows(s.dA, s.plan, A, 0, s.plan.n_rows, s.stream));
+            MVG_TRY(h2d_x(s.dx, s.plan, x, s.stream));
         }
-        if (!s.copy_ready) MVG_HIP(hipEventCreateWithFlags(&s.copy_ready, hipEventDisableTiming));
-        while ((int)s.chunk_ev.size() < nch) {
-            hipEvent_t ev;
-            MVG_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            s.chunk_ev.push_back(ev);
-        }
-        // the copies overwrite dA and dx, which the GEMV last queued on s.stream still reads
-        MVG_HIP(hipEventRecord(s.copy_ready, s.stream));
-        MVG_HIP(hipStreamWaitEvent(s.copy_stream, s.copy_ready, 0));
-        int rc = h2d_region(s.dx, x + x_off(p), x_len(p), 1, x_len(p), s.copy_stream);
-        if (rc != MVG_OK) return rc;
-        s.chunk_row.assign(nch + 1, 0);
-        for (int c = 0; c <= nch; ++c) s.chunk_row[c] = p.n_rows * c / nch;
-        for (int c = 0; c < nch; ++c) {
-            const int64_t r0 = s.chunk_row[c], r1 = s.chunk_row[c + 1];
-            rc = h2d_region(s.dA + r0 * p.n_cols, A + (p.row_off + r0) * C + p.col_off, C, r1 - r0, p.n_cols,
-                            s.copy_stream);
-            if (rc != MVG_OK) return rc;
-            MVG_HIP(hipEventRecord(s.chunk_ev[c], s.copy_stream));
-        }
-        s.chunks_pending = true;
+    }
+    e->distributed = true;
+    return MVG_OK;
+}
+
+// ---- root-send: rank 0 holds A and x and sends every peer its shard (one process per GPU)
+// A shard travels as its x segment (row0 = -1), then its rows in runs of whole rows of at
+// most kStageElems doubles. The root's sends and the peer's receives both walk this list, so
+// their counts agree call for call; empty pieces are left out on both sides.
+struct Piece {
+    int64_t row0, rows, count;
+};
+int shard_pieces(const mvg_shard& p, std::vector<Piece>* out) {
+    out->clear();
+    if (p.n_cols == 0) return MVG_OK;
+    if (p.n_cols > kStageElems) return fail(MVG_E_INVALID, "row larger than staging");
+    out->push_back({-1, 1, p.n_cols});
+    const int64_t rows_per = kStageElems / p.n_cols;
+    for (int64_t r0 = 0; r0 < p.n_rows; r0 += rows_per) {
+        const int64_t rows = std::min(rows_per, p.n_rows - r0);
+        out->push_back({r0, rows, rows * p.n_cols});
     }
     return MVG_OK;
 }
 
-// The exchange step from the shared schedule (mvg_plan_exchange): one group per step, every
-// local member issuing its call in it. A failing call inside the group still closes the group
-// before the error is reported.
-int exchange_plan(mvg_engine* e, int b, bool serial, XOps& ops) {
-    const int nsteps = e->shards[0].nsteps;
-    for (int k = 0; k < nsteps; ++k) {
-        MVG_NCCL(ops.group_start());
-        ncclResult_t r = ncclSuccess;
-        const char* what = "";
-        for (auto& s : e->shards) {
-            const mvg_xstep& st = s.steps[k];
-            if (!st.member) continue;
-            ops.set_device(s.device);
-            double* bufs[3] = {s.dy_parts[b], s.dy_row, s.dy};
-            const double* src = bufs[st.src];
-            double* dst = bufs[st.dst];
-            if (!dst) dst = s.dy_parts[b];  // recvbuff is only written on the root
-            hipStream_t stream = serial ? s.stream : s.xstream;
-            if (st.op == MVG_X_GATHER) {
-                r = ops.gather(src, dst, (size_t)st.count, st.root, s.xcomm[k], stream);
-                what = "ncclGather";
-            } else {
-                r = ops.reduce(src, dst, (size_t)st.count, st.root, s.xcomm[k], stream);
-                what = "ncclReduce";
-            }
-            if (r != ncclSuccess) break;
+hipEvent_t last_x_done(const mvg_engine* e, const Shard& s) { return s.x_done[(e->nx - 1) % e->ring]; }
+
+// Rank 0 stages each peer's shard through two device buffers and ncclSend's it over xGMI (the
+// reference's sequential root Send loop, colwise.c:33-57), overlapping the next piece's H2D
+// with the current piece's send; then copies its own shard.
+int root_send_shards(mvg_engine* e, Shard& s, const double* A, const double* x) {
+    if (!s.stage) MVG_TRY(alloc_doubles(&s.stage, 2 * kStageElems));
+    for (hipEvent_t* ev : {&s.copied[0], &s.copied[1], &s.sent[0], &s.sent[1], &s.ready}) MVG_TRY(ensure_event(ev));
+    // sent[b] starts recorded on s.stream, behind the previous GEMV (which reads dA, dx)
+    // and the caller's exchange wait: every copy_stream write below is ordered after those
+    for (int b = 0; b < 2; ++b) MVG_HIP(hipEventRecord(s.sent[b], s.stream));
+    // the own shard's copy into dA/dx needs that order even when no peer piece is sent
+    // (every peer shard empty); waiting on the initial record keeps it overlapping the
+    // last peer sends
+    MVG_HIP(hipEventRecord(s.ready, s.stream));
+    int buf = 0;
+    std::vector<Piece> pieces;
+    for (int peer = 1; peer < e->nranks; ++peer) {
+        mvg_shard p;
+        MVG_TRY(mvg_plan_shard(e->alg, e->R, e->C, e->nranks, peer, &p));
+        MVG_TRY(shard_pieces(p, &pieces));
+        for (const Piece& pc : pieces) {
+            double* stage = s.stage + buf * kStageElems;
+            MVG_HIP(hipStreamWaitEvent(s.copy_stream, s.sent[buf], 0));
+            MVG_TRY(pc.row0 < 0 ? h2d_x(stage, p, x, s.copy_stream)
+                                : h2d_rows(stage, p, A, pc.row0, pc.rows, s.copy_stream));
+            MVG_HIP(hipEventRecord(s.copied[buf], s.copy_stream));
+            MVG_HIP(hipStreamWaitEvent(s.stream, s.copied[buf], 0));
+            MVG_NCCL(ncclSend(stage, (size_t)pc.count, ncclFloat64, peer, s.world, s.stream));
+            MVG_HIP(hipEventRecord(s.sent[buf], s.stream));
+            buf ^= 1;
         }
-        const ncclResult_t r2 = ops.group_end();
-        if (r != ncclSuccess) return nccl_fail(r, what);
-        if (r2 != ncclSuccess) return nccl_fail(r2, "ncclGroupEnd");
+    }
+    // own shard last (MPI_Pack of the root's own strip comes last too, colwise.c:61-69)
+    MVG_HIP(hipStreamWaitEvent(s.copy_stream, s.ready, 0));
+    MVG_TRY(h2d_rows(s.dA, s.plan, A, 0, s.plan.n_rows, s.copy_stream));
+    MVG_TRY(h2d_x(s.dx, s.plan, x, s.copy_stream));
+    MVG_HIP(hipEventRecord(s.copied[0], s.copy_stream));
+    MVG_HIP(hipStreamWaitEvent(s.stream, s.copied[0], 0));
+    return MVG_OK;
+}
+
+// A peer receives its shard's pieces from rank 0 straight into dx and dA.
+int recv_shard(Shard& s) {
+    std::vector<Piece> pieces;
+    MVG_TRY(shard_pieces(s.plan, &pieces));
+    for (const Piece& pc : pieces)
+        MVG_NCCL(ncclRecv(pc.row0 < 0 ? s.dx : s.dA + pc.row0 * s.plan.n_cols, (size_t)pc.count, ncclFloat64, 0, s.world,
+                          s.stream));
+    return MVG_OK;
+}
+
+// The exchange step from the shared schedule (mvg_plan_exchange): one group per step, every
+// local member issuing its call in it, out of ring slot b.
+int exchange_plan(mvg_engine* e, int b, bool serial, XOps& ops) {
+    for (int k = 0; k < e->shards[0].nsteps; ++k) {
+        const char* what = e->shards[0].steps[k].op == MVG_X_GATHER ? "ncclGather" : "ncclReduce";
+        MVG_TRY(grouped(e->shards, ops, what, [&](Shard& s) {
+            const mvg_xstep& st = s.steps[k];
+            if (!st.member) return ncclSuccess;
+            ops.set_device(s.device);
+            double* bufs[3] = {s.dy_parts[b], s.dy_row, s.dy};  // by MVG_X_BUF_*
+            double* dst = bufs[st.dst] ? bufs[st.dst] : s.dy_parts[b];  // recvbuff is only written on the root
+            return ops.collective(st.op, bufs[st.src], dst, (size_t)st.count, st.root, s.xcomm[k],
+                                  serial ? s.stream : s.xstream);
+        }));
     }
     return MVG_OK;
 }
@@ -387,26 +489,23 @@ int exchange_plan(mvg_engine* e, int b, bool serial, XOps& ops) {
 // Exact mode (mvg_engine_set_exact): every partial gathered to rank 0 in rank order, then added
 // there in the reference's order.
 int exchange_exact(mvg_engine* e, int b, bool serial, XOps& ops) {
-    const int64_t count = e->alg == MVG_ALG_COLWISE ? e->R : e->shards[0].plan.y_len;
-    MVG_NCCL(ops.group_start());
-    ncclResult_t r = ncclSuccess;
-    for (auto& s : e->shards) {
+    MVG_TRY(grouped(e->shards, ops, "ncclGather (exact)", [&](Shard& s) {
         ops.set_device(s.device);
         // recvbuff is only written on the root
-        r = ops.gather(s.dy_parts[b], s.rank == 0 ? s.gbuf : s.dy_parts[b], (size_t)count, 0, s.world,
-                       serial ? s.stream : s.xstream);
-        if (r != ncclSuccess) break;
-    }
-    const ncclResult_t r2 = ops.group_end();
-    if (r != ncclSuccess) return nccl_fail(r, "ncclGather (exact)");
-    if (r2 != ncclSuccess) return nccl_fail(r2, "ncclGroupEnd");
+        return ops.collective(MVG_X_GATHER, s.dy_parts[b], s.rank == 0 ? s.gbuf : s.dy_parts[b], (size_t)s.plan.y_len, 0,
+                              s.world, serial ? s.stream : s.xstream);
+    }));
     for (auto& s : e->shards) {
         if (s.rank != 0) continue;
         ops.set_device(s.device);
-        const int rc = ops.combine(e, s, serial ? s.stream : s.xstream);
-        if (rc != MVG_OK) return rc;
+        MVG_TRY(ops.combine(e, s, serial ? s.stream : s.xstream));
     }
     return MVG_OK;
+}
+
+// One multiply's exchange out of ring slot b, as the engine and the trace both issue it.
+int exchange(mvg_engine* e, int b, bool serial, XOps& ops) {
+    return e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact(e, b, serial, ops) : exchange_plan(e, b, serial, ops);
 }
 
 // The recorder behind mvg_debug_trace_exchange. Communicators and buffers are stand-in handles
@@ -457,8 +556,9 @@ struct TraceXOps final : XOps {
         comm_step.push_back({(uintptr_t)*out, group});
         return ncclSuccess;
     }
-    ncclResult_t coll(int kind, const double* src, double* dst, size_t count, int root, ncclComm_t comm) {
-        mvg_xcall c = base(kind);
+    ncclResult_t collective(int op, const double* src, double* dst, size_t count, int root, ncclComm_t comm,
+                            hipStream_t) override {
+        mvg_xcall c = base(op == MVG_X_GATHER ? MVG_XCALL_GATHER : MVG_XCALL_REDUCE);
         c.comm = comm_of(comm);
         c.root = root;
         c.count = (int64_t)count;
@@ -467,23 +567,199 @@ struct TraceXOps final : XOps {
         calls.push_back(c);
         return ncclSuccess;
     }
-    ncclResult_t gather(const double* src, double* dst, size_t count, int root, ncclComm_t comm,
-                        hipStream_t) override {
-        return coll(MVG_XCALL_GATHER, src, dst, count, root, comm);
-    }
-    ncclResult_t reduce(const double* src, double* dst, size_t count, int root, ncclComm_t comm,
-                        hipStream_t) override {
-        return coll(MVG_XCALL_REDUCE, src, dst, count, root, comm);
-    }
     int combine(const mvg_engine* e, const Shard& s, hipStream_t) override {
         mvg_xcall c = base(MVG_XCALL_COMBINE);
-        c.count = (e->alg == MVG_ALG_COLWISE ? e->R : s.plan.y_len) * e->nranks;
+        c.count = s.plan.y_len * e->nranks;
         c.src = buf_of(s.gbuf);
         c.dst = buf_of(s.dy);
         calls.push_back(c);
         return MVG_OK;
     }
 };
+
+// ---- the steps of mvg_engine_create, per local rank
+// Plan, streams, buffers and the ring's events.
+int init_shard(mvg_engine* e, Shard& s, const LocalRank& l) {
+    s.device = l.device;
+    s.rank = l.rank;
+    s.world = l.comm;
+    MVG_TRY(mvg_plan_shard(e->alg, e->R, e->C, e->nranks, l.rank, &s.plan));
+    MVG_HIP(hipSetDevice(s.device));
+    MVG_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    MVG_HIP(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
+    MVG_TRY(alloc_doubles(&s.dA, s.plan.n_rows * s.plan.n_cols));
+    MVG_TRY(alloc_doubles(&s.dx, s.plan.n_cols));
+    MVG_TRY(mvg_plan_exchange(e->alg, e->R, e->C, e->nranks, l.rank, e->always_collect, s.steps, MVG_MAX_XSTEPS,
+                              &s.nsteps));
+    const XBufLens xb = exchange_buffers(*e, s, false);  // exact mode's buffer: mvg_engine_set_exact
+    for (int b = 0; b < (s.nsteps > 0 ? e->ring : 1); ++b) MVG_TRY(alloc_doubles(&s.dy_parts[b], xb.len[MVG_X_BUF_PART]));
+    if (s.nsteps > 0) {
+        MVG_HIP(hipStreamCreateWithFlags(&s.xstream, hipStreamNonBlocking));
+        for (int b = 0; b < e->ring; ++b) {
+            // GEMV -> exchange kernel on the same device: no system-scope fence needed (the
+            // marker with one cost ~2 us of idle GPU per multiply); exchange -> collect's
+            // D2H copy keeps the default (host-visible) fence
+            MVG_HIP(hipEventCreateWithFlags(&s.gemv_done[b], hipEventDisableTiming | hipEventDisableSystemFence));
+            MVG_TRY(ensure_event(&s.x_done[b]));
+        }
+    }
+    MVG_TRY(alloc_doubles(&s.dy_row, xb.len[MVG_X_BUF_ROW]));
+    return alloc_doubles(&s.dy, xb.len[MVG_X_BUF_Y]);
+}
+
+// Warm the device before any timed loop: first-touch every buffer (the first H2D into
+// never-touched HBM ran at 11 GB/s instead of 56, profiles/r01/e2e_small/numa_h2d.jsonl) and launch the
+// shard's GEMV once (loads its code object and any split-K workspace). These one-time
+// costs are the GPU runtime's analogue of MPI_Init; without this they landed in the
+// executables' first timed iteration (+0.1 ms on the mean at 600 x 600).
+int warm_shard(mvg_engine* e, Shard& s) {
+    const mvg_shard& p = s.plan;
+    auto zero = [&](double* d, int64_t n) -> int {
+        if (d && n > 0) MVG_HIP(hipMemsetAsync(d, 0, (size_t)n * sizeof(double), s.stream));
+        return MVG_OK;
+    };
+    MVG_TRY(zero(s.dA, p.n_rows * p.n_cols));
+    MVG_TRY(zero(s.dx, p.n_cols));
+    for (int b = 0; b < kRing; ++b) MVG_TRY(zero(s.dy_parts[b], p.y_len));
+    MVG_TRY(zero(s.dy_row, p.y_len));
+    MVG_TRY(zero(s.dy, e->R));
+    MVG_TRY(mvg_gemv(s.dA, p.n_cols, s.dx, s.dy_parts[0], p.n_rows, p.n_cols, s.stream));
+    // ... and one page-locked H2D into A's buffer and D2H out of y's, as large as those
+    // transfers will be up to 4 MiB, on each stream that distributes or collects. The
+    // runtime brings its large-copy path up on the first such transfer of the process:
+    // 8.2 ms once (tools/probes/first_copy.py: 2.88 MB from any page-locked buffer, 8.2 ms first,
+    // 66 us after; 512-B copies do not trigger it), which otherwise landed in the
+    // executables' first timed iteration (bin/multiplier_rowwise 600 600, MVG_ITER_LOG).
+    const int64_t a_elems = std::min<int64_t>(p.n_rows * p.n_cols, 1 << 19);
+    const int64_t y_elems = std::min<int64_t>(p.y_len, 1 << 19);
+    const size_t wbytes = (size_t)std::max<int64_t>({a_elems, y_elems, 1}) * sizeof(double);
+    double* pinned = nullptr;
+    if (hipHostMalloc((void**)&pinned, wbytes, hipHostMallocDefault) != hipSuccess)
+        return fail(MVG_E_NOMEM, "hipHostMalloc (engine warm-up)");
+    memset(pinned, 0, wbytes);
+    hipError_t we = hipSuccess;
+    for (hipStream_t st : {s.stream, s.copy_stream}) {
+        if (we == hipSuccess && a_elems > 0)
+            we = hipMemcpyAsync(s.dA, pinned, (size_t)a_elems * sizeof(double), hipMemcpyHostToDevice, st);
+        if (we == hipSuccess && y_elems > 0)
+            we = hipMemcpyAsync(pinned, s.dy_parts[0], (size_t)y_elems * sizeof(double), hipMemcpyDeviceToHost, st);
+        if (we == hipSuccess) we = hipStreamSynchronize(st);
+    }
+    (void)hipHostFree(pinned);
+    return we == hipSuccess ? MVG_OK : hip_fail(we, "engine warm-up");
+}
+
+// ---- the steps of mvg_engine_multiply, per local rank
+// Exact mode's panel copy of A, rebuilt from dA by the second multiply after a write: the
+// rebuild moves the shard twice through HBM (about ten multiplies' worth of the panels'
+// gain), so a distribution that is multiplied once (the reference's timed loop: distribute +
+// multiply per iteration) never pays for it, and repeated multiplies of the same A
+// (device-resident) run on panels from the second one on.
+int refresh_panels(mvg_engine* e, Shard& s, bool span_opens) {
+    if (!e->exact || !s.panelP || s.panels_fresh || s.uses < 1 || s.chunks_pending) return MVG_OK;
+    if (!s.dAp) alloc_panels(s);
+    if (!s.dAp) return MVG_OK;
+    const mvg_shard& p = s.plan;
+    MVG_TRY(mvg_panel_relayout(s.dA, p.n_cols, p.n_rows, p.n_cols, s.dAp, s.pstride, s.panelP, s.stream));
+    s.panels_fresh = true;
+    // a relayout after the span's first event would be counted as GEMV time
+    if (e->timing_every == -1 && !span_opens) e->span_valid = false;
+    return MVG_OK;
+}
+
+// The shard's product into `out`: one GEMV, or one per row chunk of a pending chunked
+// distribution (independent products: each runs once its rows have landed).
+int local_product(mvg_engine* e, Shard& s, double* out) {
+    const mvg_shard& p = s.plan;
+    const bool panels = e->exact && s.dAp && s.panels_fresh;
+    auto gemv = [&](int64_t r0, int64_t rows) {
+        if (panels)
+            return mvg_gemv_exact_panels(s.dAp + r0 * s.panelP, s.pstride, s.panelP, s.dx, out + r0, rows, p.n_cols, 0,
+                                         s.stream);
+        return e->exact ? mvg_gemv_exact(s.dA + r0 * p.n_cols, p.n_cols, s.dx, out + r0, rows, p.n_cols, s.stream)
+                        : mvg_gemv(s.dA + r0 * p.n_cols, p.n_cols, s.dx, out + r0, rows, p.n_cols, s.stream);
+    };
+    if (!s.chunks_pending) return gemv(0, p.n_rows);
+    s.chunks_pending = false;
+    for (size_t c = 0; c + 1 < s.chunk_row.size(); ++c) {
+        MVG_HIP(hipStreamWaitEvent(s.stream, s.chunk_ev[c], 0));
+        MVG_TRY(gemv(s.chunk_row[c], s.chunk_row[c + 1] - s.chunk_row[c]));
+    }
+    return MVG_OK;
+}
+
+// ---- kernel timing (mvg_engine_kernel_timing). A multiply whose GEMVs wait on a chunked
+// distribution's copies (`chunked`) is not timed in either mode.
+// Span mode (-1): one event before the first GEMV of the span, one at the next sync, no marker
+// between the GEMVs in between (a timing marker costs the stream ~6 us around the kernel it
+// brackets, profiles/r05/t5c); a chunked distribution's copies inside the span void it.
+// Counts the multiply; true when it opens the span (span_start on every shard).
+bool span_enter(mvg_engine* e, bool chunked) {
+    if (e->timing_every != -1) return false;
+    if (chunked) e->span_valid = false;
+    return e->span_multiplies++ == 0 && !chunked;
+}
+int span_start(Shard& s) {
+    if (!s.span_t0) MVG_HIP(hipEventCreate(&s.span_t0));
+    if (!s.span_t1) MVG_HIP(hipEventCreate(&s.span_t1));
+    MVG_HIP(hipEventRecord(s.span_t0, s.stream));
+    return MVG_OK;
+}
+// After a sync that recorded span_t1 on every GEMV stream: the span's GEMV time per multiply is
+// the first GEMV's start to the stream's end, max over the local devices (the GEMV stream holds
+// nothing else at one rank per process; with an exchange it also holds the once-per-ring waits
+// on the exchange stream).
+int span_close(mvg_engine* e) {
+    float worst = 0.f;
+    for (auto& s : e->shards) {
+        if (!s.span_t0 || !s.span_t1) continue;
+        float ms = 0.f;
+        MVG_HIP(hipEventElapsedTime(&ms, s.span_t0, s.span_t1));
+        worst = std::max(worst, ms);
+    }
+    if (e->span_valid) {
+        e->kernel_ms_sum += worst;
+        e->kernel_launches += e->span_multiplies;
+    }
+    e->span_multiplies = 0;
+    e->span_valid = true;
+    return MVG_OK;
+}
+
+// Per-launch mode (N > 0): every Nth multiply is bracketed by a pair of events from a pool.
+bool pool_enter(mvg_engine* e, bool chunked) {
+    return e->timing_every > 0 && (e->multiply_calls++ % e->timing_every) == 0 && !chunked;
+}
+// Records the pair's first event on the GEMV stream; the caller records *stop after the product.
+int pool_start(Shard& s, hipEvent_t* stop) {
+    if (s.ev_used == s.ev_pool.size()) {
+        hipEvent_t a, b;
+        MVG_HIP(hipEventCreate(&a));
+        MVG_HIP(hipEventCreate(&b));
+        s.ev_pool.emplace_back(a, b);
+    }
+    const auto& pair = s.ev_pool[s.ev_used++];
+    *stop = pair.second;
+    MVG_HIP(hipEventRecord(pair.first, s.stream));
+    return MVG_OK;
+}
+// After a sync: per timed multiply the max over the local devices, summed; the pool is free again.
+int pool_collect(mvg_engine* e) {
+    const size_t n = e->timing_every > 0 && !e->shards.empty() ? e->shards[0].ev_used : 0;
+    for (size_t k = 0; k < n; ++k) {
+        float worst = 0.f;
+        for (auto& s : e->shards) {
+            if (k >= s.ev_used) continue;
+            float ms = 0.f;
+            MVG_HIP(hipEventElapsedTime(&ms, s.ev_pool[k].first, s.ev_pool[k].second));
+            worst = std::max(worst, ms);
+        }
+        e->kernel_ms_sum += worst;
+        ++e->kernel_launches;
+    }
+    for (auto& s : e->shards) s.ev_used = 0;
+    return MVG_OK;
+}
 
 }  // namespace
 
@@ -526,8 +802,7 @@ int mvg_comm_init_all(mvg_comm** out, int ndev, const int* devlist) {
     // One device needs no collective (the exchange plan is empty), so RCCL is not initialised
     // at all — no bootstrap cost, no RCCL banner on the executables' stdout — unless
     // MVG_ALWAYS_COLLECT=1 asks for the collectives to run anyway.
-    const char* ac = getenv("MVG_ALWAYS_COLLECT");
-    if (ndev > 1 || (ac && ac[0] == '1')) {
+    if (ndev > 1 || getenv_flag("MVG_ALWAYS_COLLECT")) {
         MVG_NCCL(ncclCommInitAll(comms.data(), ndev, devs.data()));
     } else {
         MVG_HIP(hipSetDevice(devs[0]));
@@ -607,99 +882,23 @@ int mvg_engine_create(mvg_engine** out, int alg, int64_t R, int64_t C, mvg_comm*
     e->C = C;
     e->nranks = comm->nranks;
     e->single_process = (int)comm->locals.size() == comm->nranks;
-    const char* ac = getenv("MVG_ALWAYS_COLLECT");
     // forced collectives need an RCCL communicator (a one-device comm made without the
     // variable has none)
-    e->always_collect = ac && ac[0] == '1' && comm->locals[0].comm != nullptr;
+    e->always_collect = getenv_flag("MVG_ALWAYS_COLLECT") && comm->locals[0].comm != nullptr;
     if (const char* v = getenv("MVG_XRING")) e->ring = std::max(1, std::min(kRing, atoi(v)));
-    const char* ex = getenv("MVG_EXACT");
-    const bool want_exact = ex && ex[0] == '1';
     if (const char* ov = getenv("MVG_OVERLAP")) e->overlap_chunks = std::max(0, atoi(ov));
 
     e->shards.resize(comm->locals.size());
-    auto bail = [&](int code) {
-        mvg_engine_destroy(e);
-        return code;
-    };
-    for (size_t i = 0; i < comm->locals.size(); ++i) {
-        Shard& s = e->shards[i];
-        const LocalRank& l = comm->locals[i];
-        s.device = l.device;
-        s.rank = l.rank;
-        s.world = l.comm;
-        if ((rc = mvg_plan_shard(alg, R, C, comm->nranks, l.rank, &s.plan)) != MVG_OK) return bail(rc);
-        if (hipSetDevice(s.device) != hipSuccess) return bail(fail(MVG_E_HIP, "hipSetDevice"));
-        if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking) != hipSuccess)
-            return bail(fail(MVG_E_HIP, "hipStreamCreate"));
-        const mvg_shard& p = s.plan;
-        if ((rc = alloc_doubles(&s.dA, p.n_rows * p.n_cols)) != MVG_OK) return bail(rc);
-        if ((rc = alloc_doubles(&s.dx, x_len(p))) != MVG_OK) return bail(rc);
-        const int64_t part = alg == MVG_ALG_COLWISE ? R : p.y_len;
-        if ((rc = mvg_plan_exchange(alg, R, C, comm->nranks, l.rank, e->always_collect, s.steps,
-                                    MVG_MAX_XSTEPS, &s.nsteps)) != MVG_OK)
-            return bail(rc);
-        if ((rc = alloc_doubles(&s.dy_parts[0], part)) != MVG_OK) return bail(rc);
-        if (s.nsteps > 0) {
-            for (int b = 1; b < e->ring; ++b)
-                if ((rc = alloc_doubles(&s.dy_parts[b], part)) != MVG_OK) return bail(rc);
-            if (hipStreamCreateWithFlags(&s.xstream, hipStreamNonBlocking) != hipSuccess)
-                return bail(fail(MVG_E_HIP, "hipStreamCreate"));
-            for (int b = 0; b < e->ring; ++b)
-                // GEMV -> exchange kernel on the same device: no system-scope fence needed (the
-                // marker with one cost ~2 us of idle GPU per multiply); exchange -> collect's
-                // D2H copy keeps the default (host-visible) fence
-                if (hipEventCreateWithFlags(&s.gemv_done[b], hipEventDisableTiming | hipEventDisableSystemFence) !=
-                        hipSuccess ||
-                    hipEventCreateWithFlags(&s.x_done[b], hipEventDisableTiming) != hipSuccess)
-                    return bail(fail(MVG_E_HIP, "hipEventCreate"));
-        }
-        if (needs_row_buffer(s))
-            if ((rc = alloc_doubles(&s.dy_row, p.y_len)) != MVG_OK) return bail(rc);
-        if (l.rank == 0)
-            if ((rc = alloc_doubles(&s.dy, R)) != MVG_OK) return bail(rc);
-        // Warm the device before any timed loop: first-touch every buffer (the first H2D into
-        // never-touched HBM ran at 11 GB/s instead of 56, profiles/r01/e2e_small/numa_h2d.jsonl) and launch the
-        // shard's GEMV once (loads its code object and any split-K workspace). These one-time
-        // costs are the GPU runtime's analogue of MPI_Init; without this they landed in the
-        // executables' first timed iteration (+0.1 ms on the mean at 600 x 600).
-        auto zero = [&](double* p, int64_t n) {
-            return p && n > 0 ? hipMemsetAsync(p, 0, (size_t)n * sizeof(double), s.stream) : hipSuccess;
-        };
-        hipError_t ze = zero(s.dA, p.n_rows * p.n_cols);
-        if (ze == hipSuccess) ze = zero(s.dx, x_len(p));
-        for (int b = 0; b < kRing && ze == hipSuccess; ++b) ze = zero(s.dy_parts[b], part);
-        if (ze == hipSuccess) ze = zero(s.dy_row, p.y_len);
-        if (ze == hipSuccess) ze = zero(s.dy, R);
-        if (ze != hipSuccess) return bail(hip_fail(ze, "hipMemsetAsync"));
-        if ((rc = mvg_gemv(s.dA, p.n_cols, s.dx, s.dy_parts[0], p.n_rows, p.n_cols, s.stream)) != MVG_OK)
-            return bail(rc);
-        // ... and one page-locked H2D into A's buffer and D2H out of y's, as large as those
-        // transfers will be up to 4 MiB, on each stream that distributes or collects. The
-        // runtime brings its large-copy path up on the first such transfer of the process:
-        // 8.2 ms once (tools/probes/first_copy.py: 2.88 MB from any page-locked buffer, 8.2 ms first,
-        // 66 us after; 512-B copies do not trigger it), which otherwise landed in the
-        // executables' first timed iteration (bin/multiplier_rowwise 600 600, MVG_ITER_LOG).
-        const int64_t a_elems = std::min<int64_t>(p.n_rows * p.n_cols, 1 << 19);
-        const int64_t y_elems = std::min<int64_t>(part, 1 << 19);
-        const size_t wbytes = (size_t)std::max<int64_t>({a_elems, y_elems, 1}) * sizeof(double);
-        double* pinned = nullptr;
-        if (hipHostMalloc((void**)&pinned, wbytes, hipHostMallocDefault) != hipSuccess)
-            return bail(fail(MVG_E_NOMEM, "hipHostMalloc (engine warm-up)"));
-        memset(pinned, 0, wbytes);
-        hipError_t we = hipSuccess;
-        for (hipStream_t st : {s.stream, s.copy_stream}) {
-            if (we == hipSuccess && a_elems > 0)
-                we = hipMemcpyAsync(s.dA, pinned, (size_t)a_elems * sizeof(double), hipMemcpyHostToDevice, st);
-            if (we == hipSuccess && y_elems > 0)
-                we = hipMemcpyAsync(pinned, s.dy_parts[0], (size_t)y_elems * sizeof(double), hipMemcpyDeviceToHost, st);
-            if (we == hipSuccess) we = hipStreamSynchronize(st);
-        }
-        (void)hipHostFree(pinned);
-        if (we != hipSuccess) return bail(hip_fail(we, "engine warm-up"));
+    for (size_t i = 0; i < comm->locals.size() && rc == MVG_OK; ++i) {
+        rc = init_shard(e, e->shards[i], comm->locals[i]);
+        if (rc == MVG_OK) rc = warm_shard(e, e->shards[i]);
     }
-    if ((rc = split_steps(e->shards, g_device_ops)) != MVG_OK) return bail(rc);
-    if (want_exact && (rc = mvg_engine_set_exact(e, 1)) != MVG_OK) return bail(rc);
+    if (rc == MVG_OK) rc = split_steps(e->shards, g_device_ops);
+    if (rc == MVG_OK && getenv_flag("MVG_EXACT")) rc = mvg_engine_set_exact(e, 1);
+    if (rc != MVG_OK) {
+        mvg_engine_destroy(e);
+        return rc;
+    }
     *out = e;
     return MVG_OK;
 }
@@ -714,31 +913,28 @@ int mvg_engine_create(mvg_engine** out, int alg, int64_t R, int64_t C, mvg_comm*
 // when the grid has at most two columns).
 int mvg_engine_set_exact(mvg_engine* e, int on) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
-    int rc = mvg_engine_sync(e);
-    if (rc != MVG_OK) return rc;
-    e->exact = on != 0;
+    MVG_TRY(mvg_engine_sync(e));
+    const bool exact = on != 0;
     DeviceGuard g;
+    // whatever can fail comes first: an error leaves the mode and the panel fields as they were
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
-        if (!e->exact) {
+        if (!s.gbuf) MVG_TRY(alloc_doubles(&s.gbuf, exchange_buffers(*e, s, exact).len[MVG_X_BUF_GATHERED]));
+    }
+    e->exact = exact;
+    for (auto& s : e->shards) {
+        (void)hipSetDevice(s.device);
+        if (!exact) {
             if (s.dAp) (void)hipFree(s.dAp);
             s.dAp = nullptr;
             s.panelP = s.pstride = 0;
-            continue;
+        } else if (!s.dAp && !getenv_flag("MVG_NO_PANELS")) {
+            // the panel copy where it pays (mvg_exact_panel_width); allocated by the multiply that
+            // first needs it (alloc_panels), so a distribute-per-multiply loop never holds one
+            s.panelP = mvg_exact_panel_width(s.plan.n_rows, s.plan.n_cols);
+            s.pstride = s.plan.n_rows * s.panelP;
+            s.panels_fresh = false;
         }
-        if (s.dAp || getenv_flag("MVG_NO_PANELS")) continue;
-        // the panel copy where it pays (mvg_exact_panel_width); allocated by the multiply that
-        // first needs it (alloc_panels), so a distribute-per-multiply loop never holds one
-        s.panelP = mvg_exact_panel_width(s.plan.n_rows, s.plan.n_cols);
-        s.pstride = s.plan.n_rows * s.panelP;
-        s.panels_fresh = false;
-    }
-    if (!e->exact || e->alg == MVG_ALG_ROWWISE) return MVG_OK;
-    for (auto& s : e->shards) {
-        if (s.rank != 0 || s.nsteps == 0 || s.gbuf) continue;
-        MVG_HIP(hipSetDevice(s.device));
-        const int64_t part = e->alg == MVG_ALG_COLWISE ? e->R : s.plan.y_len;
-        if ((rc = alloc_doubles(&s.gbuf, part * e->nranks)) != MVG_OK) return rc;
     }
     return MVG_OK;
 }
@@ -757,8 +953,7 @@ int mvg_engine_exact(const mvg_engine* e, int* on) {
 
 int mvg_engine_set_overlap(mvg_engine* e, int chunks) {
     if (!e || chunks < 0) return fail(MVG_E_INVALID, "mvg_engine_set_overlap: bad arguments");
-    int rc = mvg_engine_sync(e);
-    if (rc != MVG_OK) return rc;
+    MVG_TRY(mvg_engine_sync(e));
     e->overlap_chunks = chunks;
     return MVG_OK;
 }
@@ -775,29 +970,16 @@ int mvg_engine_stream(const mvg_engine* e, int i, void** stream) {
     return MVG_OK;
 }
 
-// A write of the shard (distribution, synthetic fill) while a kernel-timing span is open would
-// land on the GEMV stream between the span's events: the span no longer times GEMVs alone.
-static void void_open_span(mvg_engine* e) {
-    if (e->timing_every == -1 && e->span_multiplies > 0) e->span_valid = false;
-}
-
 int mvg_engine_fill_synth(mvg_engine* e, uint64_t seed_a, uint64_t seed_x) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
-    void_open_span(e);
+    begin_write(e);
     DeviceGuard g;
-    int rc;
     for (auto& s : e->shards) {
-        s.panels_fresh = false;
-        s.uses = 0;
         MVG_HIP(hipSetDevice(s.device));
-        if ((rc = drain_chunks(s)) != MVG_OK) return rc;
+        MVG_TRY(drain_chunks(s));
         const mvg_shard& p = s.plan;
-        if ((rc = mvg_synth_fill_device(s.dA, p.n_cols, p.n_rows, p.n_cols, p.row_off, p.col_off,
-                                        e->C, seed_a, s.stream)) != MVG_OK)
-            return rc;
-        if ((rc = mvg_synth_fill_device(s.dx, x_len(p), 1, x_len(p), 0, x_off(p), e->C, seed_x,
-                                        s.stream)) != MVG_OK)
-            return rc;
+        MVG_TRY(mvg_synth_fill_device(s.dA, p.n_cols, p.n_rows, p.n_cols, p.row_off, p.col_off, e->C, seed_a, s.stream));
+        MVG_TRY(mvg_synth_fill_device(s.dx, p.n_cols, 1, p.n_cols, 0, p.col_off, e->C, seed_x, s.stream));
     }
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
@@ -808,110 +990,24 @@ int mvg_engine_fill_synth(mvg_engine* e, uint64_t seed_a, uint64_t seed_x) {
 }
 
 // Root (rank 0's process) holds A and x in host memory, as in every reference driver.
-// Single-process: each device pulls its own shard over its own PCIe link, concurrently.
-// One process per GPU: rank 0 stages each peer's shard through two device buffers and
-// ncclSend's it over xGMI (the reference's sequential root Send loop, colwise.c:33-57),
-// overlapping the next chunk's H2D with the current chunk's send.
+// Single-process: each device pulls its own shard over its own PCIe link (distribute_direct).
+// One process per GPU: rank 0 sends every peer its shard (root_send_shards / recv_shard).
 int mvg_engine_distribute(mvg_engine* e, const double* A, const double* x) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
-    void_open_span(e);
+    bool root = false;
+    for (auto& s : e->shards) root |= s.rank == 0;
+    if (root && (!x || (!A && e->R * e->C > 0))) return fail(MVG_E_INVALID, "root needs A and x");
+    if (e->single_process) return distribute_direct(e, A, x);
+    begin_write(e);
     DeviceGuard g;
-    const int64_t C = e->C;
-    Shard* root = nullptr;
-    for (auto& s : e->shards)
-        if (s.rank == 0) root = &s;
-    if (root && (!x || (!A && e->R * C > 0))) return fail(MVG_E_INVALID, "root needs A and x");
-    for (auto& s : e->shards) s.panels_fresh = false, s.uses = 0;
-
-    if (e->single_process) {
-        int rc = distribute_direct(e, A, x);
-        if (rc != MVG_OK) return rc;
-    } else {
-        // exactly one local shard
-        Shard& s = e->shards[0];
-        MVG_HIP(hipSetDevice(s.device));
-        // the root-send form always lands whole shards on s.stream, after any chunked copies
-        if (int rc0 = drain_chunks(s); rc0 != MVG_OK) return rc0;
-        // the sends/recvs below use the world communicator on s.stream: order them after any
-        // exchange still running on s.xstream (one communicator, one order of operations)
-        if (e->x_pending) MVG_HIP(hipStreamWaitEvent(s.stream, s.x_done[(e->nx - 1) % e->ring], 0));
-        if (s.rank == 0) {
-            const int64_t chunk_bytes = 256ll << 20;
-            if (!s.stage[0]) {
-                s.stage_elems = (size_t)(chunk_bytes / (int64_t)sizeof(double));
-                int rc;
-                if ((rc = alloc_doubles(&s.stage[0], (int64_t)s.stage_elems)) != MVG_OK) return rc;
-                if ((rc = alloc_doubles(&s.stage[1], (int64_t)s.stage_elems)) != MVG_OK) return rc;
-            }
-            // sent[b] starts recorded on s.stream, behind the previous GEMV (which reads dA, dx)
-            // and the exchange wait above: every copy_stream write below is ordered after those
-            hipEvent_t copied[2], sent[2];
-            for (int b = 0; b < 2; ++b) {
-                MVG_HIP(hipEventCreateWithFlags(&copied[b], hipEventDisableTiming));
-                MVG_HIP(hipEventCreateWithFlags(&sent[b], hipEventDisableTiming));
-                MVG_HIP(hipEventRecord(sent[b], s.stream));
-            }
-            // the own shard's copy into dA/dx needs that order even when no peer piece is sent
-            // (every peer shard empty); waiting on the initial record keeps it overlapping the
-            // last peer sends
-            hipEvent_t ready;
-            MVG_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
-            MVG_HIP(hipEventRecord(ready, s.stream));
-            int buf = 0;
-            for (int peer = 1; peer < e->nranks; ++peer) {
-                mvg_shard p;
-                int rc = mvg_plan_shard(e->alg, e->R, C, e->nranks, peer, &p);
-                if (rc != MVG_OK) return rc;
-                // x segment first, then A rows in chunks
-                struct Piece { const double* src; int64_t ld, rows, cols; };
-                std::vector<Piece> pieces;
-                pieces.push_back({x + x_off(p), x_len(p), 1, x_len(p)});
-                const int64_t rows_per = p.n_cols > 0
-                    ? std::max<int64_t>(1, (int64_t)s.stage_elems / p.n_cols) : p.n_rows;
-                for (int64_t r0 = 0; r0 < p.n_rows; r0 += rows_per)
-                    pieces.push_back({A + (p.row_off + r0) * C + p.col_off, C,
-                                      std::min(rows_per, p.n_rows - r0), p.n_cols});
-                for (const Piece& pc : pieces) {
-                    const int64_t n = pc.rows * pc.cols;
-                    if (n == 0) continue;
-                    if (n > (int64_t)s.stage_elems) return fail(MVG_E_INVALID, "row larger than staging");
-                    MVG_HIP(hipStreamWaitEvent(s.copy_stream, sent[buf], 0));
-                    if ((rc = h2d_region(s.stage[buf], pc.src, pc.ld, pc.rows, pc.cols, s.copy_stream)) != MVG_OK)
-                        return rc;
-                    MVG_HIP(hipEventRecord(copied[buf], s.copy_stream));
-                    MVG_HIP(hipStreamWaitEvent(s.stream, copied[buf], 0));
-                    MVG_NCCL(ncclSend(s.stage[buf], (size_t)n, ncclFloat64, peer, s.world, s.stream));
-                    MVG_HIP(hipEventRecord(sent[buf], s.stream));
-                    buf ^= 1;
-                }
-            }
-            // own shard last (MPI_Pack of the root's own strip comes last too, colwise.c:61-69)
-            const mvg_shard& p = s.plan;
-            MVG_HIP(hipStreamWaitEvent(s.copy_stream, ready, 0));
-            (void)hipEventDestroy(ready);
-            int rc = h2d_region(s.dA, A + p.row_off * C + p.col_off, C, p.n_rows, p.n_cols, s.copy_stream);
-            if (rc != MVG_OK) return rc;
-            if ((rc = h2d_region(s.dx, x + x_off(p), x_len(p), 1, x_len(p), s.copy_stream)) != MVG_OK) return rc;
-            MVG_HIP(hipEventRecord(copied[0], s.copy_stream));
-            MVG_HIP(hipStreamWaitEvent(s.stream, copied[0], 0));
-            for (int b = 0; b < 2; ++b) {
-                (void)hipEventDestroy(copied[b]);
-                (void)hipEventDestroy(sent[b]);
-            }
-        } else {
-            const mvg_shard& p = s.plan;
-            if (x_len(p) > 0)
-                MVG_NCCL(ncclRecv(s.dx, (size_t)x_len(p), ncclFloat64, 0, s.world, s.stream));
-            const int64_t rows_per = p.n_cols > 0
-                ? std::max<int64_t>(1, (int64_t)((256ll << 20) / (int64_t)sizeof(double)) / p.n_cols)
-                : p.n_rows;
-            for (int64_t r0 = 0; r0 < p.n_rows; r0 += rows_per) {
-                const int64_t n = std::min(rows_per, p.n_rows - r0) * p.n_cols;
-                if (n == 0) continue;
-                MVG_NCCL(ncclRecv(s.dA + r0 * p.n_cols, (size_t)n, ncclFloat64, 0, s.world, s.stream));
-            }
-        }
-    }
+    Shard& s = e->shards[0];  // exactly one local shard
+    MVG_HIP(hipSetDevice(s.device));
+    // the root-send form always lands whole shards on s.stream, after any chunked copies
+    MVG_TRY(drain_chunks(s));
+    // the sends/recvs use the world communicator on s.stream: order them after any exchange
+    // still running on s.xstream (one communicator, one order of operations)
+    if (e->x_pending) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+    MVG_TRY(s.rank == 0 ? root_send_shards(e, s, A, x) : recv_shard(s));
     e->distributed = true;
     return MVG_OK;
 }
@@ -919,19 +1015,12 @@ int mvg_engine_distribute(mvg_engine* e, const double* A, const double* x) {
 int mvg_engine_distribute_shared(mvg_engine* e, const double* A, const double* x) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
     if (!x || (!A && e->R * e->C > 0)) return fail(MVG_E_INVALID, "every rank needs the shared A and x");
-    void_open_span(e);
-    for (auto& s : e->shards) s.panels_fresh = false, s.uses = 0;
-    DeviceGuard g;
-    int rc = distribute_direct(e, A, x);
-    if (rc != MVG_OK) return rc;
-    e->distributed = true;
-    return MVG_OK;
+    return distribute_direct(e, A, x);
 }
 
 int mvg_engine_kernel_timing(mvg_engine* e, int enable) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
-    int rc = mvg_engine_sync(e);
-    if (rc != MVG_OK) return rc;
+    MVG_TRY(mvg_engine_sync(e));
     e->timing_every = enable > 0 ? enable : enable == -1 ? -1 : 0;
     e->span_multiplies = 0;
     e->span_valid = true;
@@ -945,99 +1034,38 @@ int mvg_engine_multiply(mvg_engine* e) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
     if (!e->distributed) return fail(MVG_E_STATE, "mvg_engine_multiply before distribute/fill");
     DeviceGuard g;
-    const int nsteps = e->shards[0].nsteps;
-    const bool solo = nsteps == 0;  // P == 1: the product goes straight into y
+    const bool solo = e->shards[0].nsteps == 0;  // P == 1: the product goes straight into y
+    const bool serial = e->ring == 1;
     bool chunked = false;  // a chunked distribution is pending: the GEMVs wait on copies, not timed
     for (auto& s : e->shards) chunked |= s.chunks_pending;
-    const bool timed = e->timing_every > 0 && (e->multiply_calls++ % e->timing_every) == 0 && !chunked;
-    // span timing: one event before the first GEMV of the span, one at the next sync, no marker
-    // between the GEMVs in between (a timing marker costs the stream ~6 us around the kernel it
-    // brackets, profiles/r05/t5c); a chunked distribution's copies inside the span void it
-    const bool span_open = e->timing_every == -1 && e->span_multiplies == 0 && !chunked;
-    if (e->timing_every == -1) {
-        if (chunked) e->span_valid = false;
-        ++e->span_multiplies;
-    }
-    const bool serial = e->ring == 1;
+    const bool timed = pool_enter(e, chunked);
+    const bool span_opens = span_enter(e, chunked);
     const int b = solo ? 0 : (int)(e->nx % e->ring);
     // The GEMV writes dy_parts[b]; the exchange that last read it was multiply nx - ring's. The
     // GEMV stream waits once per ring, on the latest exchange (nx - 1): every slot is then free
     // for the next `ring` GEMVs (the exchange stream runs in order), so one cross-stream wait is
     // paid per ring instead of per multiply (measured: a wait per multiply cost more than the
     // overlap saved at world size 1).
-    int wait_slot = -1;
-    if (!solo && !serial && e->x_pending && b == 0) wait_slot = (int)((e->nx - 1) % e->ring);
+    const bool wait_ring = !solo && !serial && e->x_pending && b == 0;
     // 1) local product on every device
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
-        const mvg_shard& p = s.plan;
-        if (wait_slot >= 0) MVG_HIP(hipStreamWaitEvent(s.stream, s.x_done[wait_slot], 0));
-        double* out = solo ? s.dy : s.dy_parts[b];
-        // exact mode's panel copy of A, rebuilt from dA by the second multiply after a write:
-        // the rebuild moves the shard twice through HBM (about ten multiplies' worth of the
-        // panels' gain), so a distribution that is multiplied once (the reference's timed loop:
-        // distribute + multiply per iteration) never pays for it, and repeated multiplies of
-        // the same A (device-resident) run on panels from the second one on
-        if (e->exact && s.panelP && !s.panels_fresh && s.uses >= 1 && !s.chunks_pending) {
-            if (!s.dAp) alloc_panels(s);
-            if (s.dAp) {
-                int rc = mvg_panel_relayout(s.dA, p.n_cols, p.n_rows, p.n_cols, s.dAp, s.pstride, s.panelP, s.stream);
-                if (rc != MVG_OK) return rc;
-                s.panels_fresh = true;
-                // a relayout after the span's first event would be counted as GEMV time
-                if (e->timing_every == -1 && !span_open) e->span_valid = false;
-            }
-        }
-        const bool panels = e->exact && s.dAp && s.panels_fresh;
+        if (wait_ring) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+        MVG_TRY(refresh_panels(e, s, span_opens));
         ++s.uses;
-        if (span_open) {
-            if (!s.span_t0) MVG_HIP(hipEventCreate(&s.span_t0));
-            if (!s.span_t1) MVG_HIP(hipEventCreate(&s.span_t1));
-            MVG_HIP(hipEventRecord(s.span_t0, s.stream));
-        }
-        hipEvent_t t0 = nullptr, t1 = nullptr;
-        if (timed) {
-            if (s.ev_used == s.ev_pool.size()) {
-                hipEvent_t a, b;
-                MVG_HIP(hipEventCreate(&a));
-                MVG_HIP(hipEventCreate(&b));
-                s.ev_pool.emplace_back(a, b);
-            }
-            t0 = s.ev_pool[s.ev_used].first;
-            t1 = s.ev_pool[s.ev_used].second;
-            ++s.ev_used;
-            MVG_HIP(hipEventRecord(t0, s.stream));
-        }
-        auto gemv = [&](int64_t r0, int64_t rows) {
-            if (panels)
-                return mvg_gemv_exact_panels(s.dAp + r0 * s.panelP, s.pstride, s.panelP, s.dx, out + r0, rows,
-                                             p.n_cols, 0, s.stream);
-            return e->exact ? mvg_gemv_exact(s.dA + r0 * p.n_cols, p.n_cols, s.dx, out + r0, rows, p.n_cols, s.stream)
-                            : mvg_gemv(s.dA + r0 * p.n_cols, p.n_cols, s.dx, out + r0, rows, p.n_cols, s.stream);
-        };
-        int rc = MVG_OK;
-        if (s.chunks_pending) {
-            // row chunks are independent products: each runs once its rows have landed
-            for (size_t c = 0; c + 1 < s.chunk_row.size() && rc == MVG_OK; ++c) {
-                MVG_HIP(hipStreamWaitEvent(s.stream, s.chunk_ev[c], 0));
-                rc = gemv(s.chunk_row[c], s.chunk_row[c + 1] - s.chunk_row[c]);
-            }
-            s.chunks_pending = false;
-        } else {
-            rc = gemv(0, p.n_rows);
-        }
-        if (rc != MVG_OK) return rc;
-        if (timed) MVG_HIP(hipEventRecord(t1, s.stream));
-        if (!solo && !serial) {
+        hipEvent_t stop = nullptr;
+        if (span_opens) MVG_TRY(span_start(s));
+        if (timed) MVG_TRY(pool_start(s, &stop));
+        MVG_TRY(local_product(e, s, solo ? s.dy : s.dy_parts[b]));
+        if (stop) MVG_HIP(hipEventRecord(stop, s.stream));
+        if (!solo && !serial) {  // hand over to the exchange stream
             MVG_HIP(hipEventRecord(s.gemv_done[b], s.stream));
             MVG_HIP(hipStreamWaitEvent(s.xstream, s.gemv_done[b], 0));
         }
     }
     if (solo) return MVG_OK;
     // 2) the exchange step on the exchange stream, overlapping the next multiply's GEMV
-    const int rc_x = e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact(e, b, serial, g_device_ops)
-                                                            : exchange_plan(e, b, serial, g_device_ops);
-    if (rc_x != MVG_OK) return rc_x;
+    MVG_TRY(exchange(e, b, serial, g_device_ops));
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
         if (!serial) MVG_HIP(hipEventRecord(s.x_done[b], s.xstream));
@@ -1050,7 +1078,7 @@ int mvg_engine_multiply(mvg_engine* e) {
 int mvg_engine_sync(mvg_engine* e) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
     DeviceGuard g;
-    const bool span = e->timing_every == -1 && e->span_multiplies > 0;
+    const bool span = span_is_open(e);
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
         if (span && s.span_t1) MVG_HIP(hipEventRecord(s.span_t1, s.stream));
@@ -1059,47 +1087,13 @@ int mvg_engine_sync(mvg_engine* e) {
         if (s.xstream) MVG_HIP(hipStreamSynchronize(s.xstream));
     }
     e->x_pending = false;
-    if (span) {
-        // the span's GEMV time per multiply: first GEMV's start to the stream's end, max over
-        // the local devices (the GEMV stream holds nothing else at one rank per process; with an
-        // exchange it also holds the once-per-ring waits on the exchange stream)
-        float worst = 0.f;
-        for (auto& s : e->shards) {
-            if (!s.span_t0 || !s.span_t1) continue;
-            float ms = 0.f;
-            MVG_HIP(hipEventElapsedTime(&ms, s.span_t0, s.span_t1));
-            worst = std::max(worst, ms);
-        }
-        if (e->span_valid) {
-            e->kernel_ms_sum += worst;
-            e->kernel_launches += e->span_multiplies;
-        }
-        e->span_multiplies = 0;
-        e->span_valid = true;
-    }
-    if (e->timing_every > 0) {
-        // per timed multiply call: max over local devices, then summed
-        size_t n = e->shards.empty() ? 0 : e->shards[0].ev_used;
-        for (size_t k = 0; k < n; ++k) {
-            float worst = 0.f;
-            for (auto& s : e->shards) {
-                if (k >= s.ev_used) continue;
-                float ms = 0.f;
-                MVG_HIP(hipEventElapsedTime(&ms, s.ev_pool[k].first, s.ev_pool[k].second));
-                worst = std::max(worst, ms);
-            }
-            e->kernel_ms_sum += worst;
-            ++e->kernel_launches;
-        }
-    }
-    for (auto& s : e->shards) s.ev_used = 0;
-    return MVG_OK;
+    if (span) MVG_TRY(span_close(e));
+    return pool_collect(e);
 }
 
 int mvg_engine_kernel_ms(mvg_engine* e, double* avg_ms, int64_t* launches) {
     if (!e || !avg_ms) return fail(MVG_E_INVALID, "null");
-    int rc = mvg_engine_sync(e);
-    if (rc != MVG_OK) return rc;
+    MVG_TRY(mvg_engine_sync(e));
     *avg_ms = e->kernel_launches ? e->kernel_ms_sum / (double)e->kernel_launches : 0.0;
     if (launches) *launches = e->kernel_launches;
     return MVG_OK;
@@ -1113,7 +1107,7 @@ int mvg_engine_collect(mvg_engine* e, double* y) {
         if (!y) return fail(MVG_E_INVALID, "root needs a y buffer");
         MVG_HIP(hipSetDevice(s.device));
         if (e->x_pending)  // y is complete once the last exchange is
-            MVG_HIP(hipStreamWaitEvent(s.stream, s.x_done[(e->nx - 1) % e->ring], 0));
+            MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
         if (e->R > 0)
             MVG_HIP(hipMemcpyAsync(y, s.dy, (size_t)e->R * sizeof(double), hipMemcpyDeviceToHost, s.stream));
         MVG_HIP(hipStreamSynchronize(s.stream));
@@ -1124,14 +1118,11 @@ int mvg_engine_collect(mvg_engine* e, double* y) {
 // The single-process G-device exchange (the executables' MVG_NGPUS=G form) without devices:
 // the shards the engine would create over G local devices (the same planner, the same buffer
 // choices), their communicator splits and one multiply's exchange, issued through the recorder
-// instead of RCCL (split_steps, exchange_plan / exchange_exact: the engine's own code).
+// instead of RCCL (exchange_buffers, split_steps, exchange: the engine's own code).
 int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, mvg_xcall* calls, int max_calls,
                              int* ncalls) {
     if (!calls || !ncalls || ndev <= 0 || max_calls < 0) return fail(MVG_E_INVALID, "mvg_debug_trace_exchange: bad arguments");
     *ncalls = 0;
-    mvg_shard probe;
-    int rc = mvg_plan_shard(alg, R, C, ndev, 0, &probe);
-    if (rc != MVG_OK) return rc;
     mvg_engine e;
     e.alg = alg;
     e.R = R;
@@ -1152,18 +1143,15 @@ int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact,
         s.rank = r;
         s.world = (ncclComm_t)((uintptr_t)0x7d0000 + r);
         ops.comm_step.push_back({(uintptr_t)s.world, -1});
-        if ((rc = mvg_plan_shard(alg, R, C, ndev, r, &s.plan)) != MVG_OK) return rc;
-        if ((rc = mvg_plan_exchange(alg, R, C, ndev, r, 0, s.steps, MVG_MAX_XSTEPS, &s.nsteps)) != MVG_OK) return rc;
-        s.dy_parts[0] = fake(r, MVG_X_BUF_PART);
-        if (needs_row_buffer(s)) s.dy_row = fake(r, MVG_X_BUF_ROW);
-        if (r == 0) s.dy = fake(r, MVG_X_BUF_Y);
-        if (e.exact && alg != MVG_ALG_ROWWISE && r == 0 && s.nsteps > 0) s.gbuf = fake(r, MVG_X_BUF_GATHERED);
+        MVG_TRY(mvg_plan_shard(alg, R, C, ndev, r, &s.plan));
+        MVG_TRY(mvg_plan_exchange(alg, R, C, ndev, r, 0, s.steps, MVG_MAX_XSTEPS, &s.nsteps));
+        const XBufLens xb = exchange_buffers(e, s, e.exact);
+        double** slot[4] = {&s.dy_parts[0], &s.dy_row, &s.dy, &s.gbuf};  // by MVG_X_BUF_*
+        for (int id = 0; id < 4; ++id)
+            if (xb.len[id] >= 0) *slot[id] = fake(r, id);
     }
-    if ((rc = split_steps(e.shards, ops)) != MVG_OK) return rc;
-    if (e.shards[0].nsteps > 0) {
-        rc = e.exact && alg != MVG_ALG_ROWWISE ? exchange_exact(&e, 0, false, ops) : exchange_plan(&e, 0, false, ops);
-        if (rc != MVG_OK) return rc;
-    }
+    MVG_TRY(split_steps(e.shards, ops));
+    if (e.shards[0].nsteps > 0) MVG_TRY(exchange(&e, 0, false, ops));
     if ((int)ops.calls.size() > max_calls) return fail(MVG_E_INVALID, "mvg_debug_trace_exchange: calls buffer too small");
     for (size_t i = 0; i < ops.calls.size(); ++i) calls[i] = ops.calls[i];
     *ncalls = (int)ops.calls.size();

@@ -2,10 +2,12 @@
 
 One process per rank, every rank on GPU 0 (on a one-GPU box RCCL needs a distinct NCCL_HOSTID
 per rank and loopback sockets, as bench.py's MVG_SAME_DEVICE rehearsal does). For each
-algorithm: distribute(A1, x1) -> multiply -> distribute(A2, x2) -> multiply -> collect, with
-no engine sync in between. The root's second distribute overwrites dA/dx (own shard) and the
-staging buffers (peer sends) while the first multiply's GEMV and exchange may still be in
-flight, so y equals A2·x2 only if the engine orders those copies after them.
+algorithm: distribute(A2, x2) -> multiply -> distribute(A1, x1) -> multiply -> distribute(A2, x2)
+-> multiply -> collect, with no engine sync in between. Each later distribute overwrites dA/dx
+(own shard) and the staging buffers (peer sends) while the previous multiply's GEMV and exchange
+may still be in flight, so y equals A2·x2 only if the engine orders those copies after them. The
+root's staging buffers and ordering events are made by the first distribute and used again by
+the second and the third.
 Prints one JSON line per algorithm on rank 0.
 """
 import json
@@ -40,10 +42,9 @@ def main():
         for alg in ("rowwise", "colwise", "blockwise"):
             with mm.Multiplier(alg, R, C, comm) as e:
                 root = e.is_root()
-                e.distribute(A1 if root else None, x1 if root else None)
-                e.multiply()
-                e.distribute(A2 if root else None, x2 if root else None)
-                e.multiply()
+                for A, x in ((A2, x2), (A1, x1), (A2, x2)):
+                    e.distribute(A if root else None, x if root else None)
+                    e.multiply()
                 y = e.collect()
             if root:
                 want = oracle.multiply(alg, A2, x2, world)

@@ -1,6 +1,7 @@
 """C-ABI library: loads, exports every declared symbol, and its host-only logic (planner,
 exchange schedule, synthetic generator, text I/O) matches the reference's behaviour. No GPU."""
 import ctypes as C
+import json
 import os
 import re
 
@@ -159,6 +160,35 @@ def test_exchange_solo_has_no_steps_unless_forced():
     for alg in ("rowwise", "colwise", "blockwise"):
         assert mm.plan_exchange(alg, 8, 8, 1, 0) == []
         assert len(mm.plan_exchange(alg, 8, 8, 1, 0, force_collect=True)) == 1
+
+
+def test_exchange_trace_matches_the_recorded_fixture():
+    """The engine's single-process exchange (which buffers each rank owns, which exchange it picks,
+    the order of the splits, collectives and combine) against tests/golden/exchange_traces.json,
+    call for call and field for field: every algorithm, G = 1, 2, 3, 4, 6, 8, tree and exact."""
+    with open(os.path.join(GOLDEN_DIR, "exchange_traces.json")) as f:
+        fixture = json.load(f)
+    R, Cn = fixture["R"], fixture["C"]
+    assert (R, Cn) == (96, 96)
+    fields = [name for name, _ in _lib.XCall._fields_]
+    assert fixture["fields"] == fields  # every field of mvg_xcall is compared
+    keys = []
+    for alg in ("rowwise", "colwise", "blockwise"):
+        for G in (1, 2, 3, 4, 6, 8):
+            for exact in (False, True):
+                key = f"{alg}/G{G}/{'exact' if exact else 'tree'}"
+                keys.append(key)
+                got = [[c[f] for f in fields] for c in mm.trace_exchange(alg, R, Cn, G, exact=exact)]
+                want = fixture["traces"][key]
+                assert len(got) == len(want), key
+                for i, (g, w) in enumerate(zip(got, want)):
+                    assert g == w, (key, i, dict(zip(fields, g)), dict(zip(fields, w)))
+    assert sorted(keys) == sorted(fixture["traces"])
+    # G = 1 has no exchange; every other case records calls, two levels on the 2 x 3 and 2 x 4 grids
+    assert all((len(fixture["traces"][k]) == 0) == ("/G1/" in k) for k in keys)
+    for G in (6, 8):
+        splits = [c for c in fixture["traces"][f"blockwise/G{G}/tree"] if c[1] == _lib.XCALL_SPLIT]
+        assert len(splits) == 2 * G
 
 
 # ---------------------------------------------------------------- synthetic generator

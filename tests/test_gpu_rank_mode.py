@@ -1,5 +1,5 @@
 """One-process-per-GPU engine paths run back to back without an engine sync:
-distribute -> multiply -> distribute -> multiply -> collect must give A2·x2, at world size 1
+(distribute -> multiply) three times, then collect, must give the last A·x, at world size 1
 (every device pulls its own shard) and at world size 2 with both ranks on GPU 0 (the root
 stages its peer's shard and ncclSends it; its own shard is copied on the copy stream, which
 must wait for the previous GEMV still reading dA/dx)."""
