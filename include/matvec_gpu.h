@@ -251,6 +251,14 @@ int mvg_debug_set_exact_even_lds(int64_t bytes);
  * hipDeviceAttributeMaxSharedMemoryPerBlock, logged once on stderr): the auto dispatch there
  * then runs the one-wave forms. 0 otherwise; MVG_E_INVALID for a device index outside 0..63. */
 int mvg_gemv_exact_even_refused(int device);
+/* Test hooks: exact mode's combine kernels on their own, as the engine launches them on rank 0
+ * after the gather of the partials (device pointers, asynchronous on `stream`).
+ * mvg_debug_combine_mpich: d_parts[r*n + i] = rank r's partial y (P ranks of n doubles); d_y[i] =
+ * their sum in the order MPICH 3.3.2's MPI_Reduce adds them (colwise.c:124). d_parts is
+ * overwritten. mvg_debug_combine_grid_rows: d_parts[r*lr + j] = rank r's partial on a gr x gc
+ * grid; d_y[g*lr + j] = ((0 + p[g*gc]) + p[g*gc + 1]) + ... (blockwise.c:150-207). */
+int mvg_debug_combine_mpich(double* d_parts, int P, int64_t n, double* d_y, void* stream);
+int mvg_debug_combine_grid_rows(const double* d_parts, int gr, int gc, int64_t lr, double* d_y, void* stream);
 
 /* The same bit-exact product over A in column panels (the engine's device layout in exact mode,
  * DESIGN §4b): panel p holds columns [p*P, p*P + P) of all m rows, row i of it at

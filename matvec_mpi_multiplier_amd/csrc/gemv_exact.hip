@@ -946,6 +946,22 @@ int mvg_debug_set_exact_even_lds(int64_t bytes) {
     return MVG_OK;
 }
 
+int mvg_debug_combine_mpich(double* parts, int P, int64_t n, double* y, void* stream) {
+    if (P <= 0 || n < 0) return fail(MVG_E_INVALID, "mvg_debug_combine_mpich: bad rank count or length");
+    if (n == 0) return MVG_OK;
+    if (!parts || !y) return fail(MVG_E_INVALID, "mvg_debug_combine_mpich: null pointer");
+    if (int rc = take_pending_error("mvg_debug_combine_mpich"); rc != MVG_OK) return rc;
+    return launch_combine_mpich_reduce(parts, P, n, y, (hipStream_t)stream);
+}
+
+int mvg_debug_combine_grid_rows(const double* parts, int gr, int gc, int64_t lr, double* y, void* stream) {
+    if (gr <= 0 || gc <= 0 || lr < 0) return fail(MVG_E_INVALID, "mvg_debug_combine_grid_rows: bad grid or length");
+    if (lr == 0) return MVG_OK;
+    if (!parts || !y) return fail(MVG_E_INVALID, "mvg_debug_combine_grid_rows: null pointer");
+    if (int rc = take_pending_error("mvg_debug_combine_grid_rows"); rc != MVG_OK) return rc;
+    return launch_combine_grid_rows(parts, gr, gc, lr, y, (hipStream_t)stream);
+}
+
 int mvg_gemv_exact(const double* A, int64_t lda, const double* x, double* y, int64_t m, int64_t k,
                    void* stream) {
     return mvg_gemv_exact_variant(A, lda, x, y, m, k, 0, stream);

@@ -405,6 +405,66 @@ def test_engine_exact_panels_fill_synth_and_toggle(comm1):
         assert oracle.multiply_std_rowwise(Ar, x)[0] == y1[r], r
 
 
+# ---------------------------------------------------------------- the exact combines, on the device
+# combine_mpich / combine_grid_rows (csrc/gemv_exact.hip) through their test hooks, at rank counts
+# no single box reaches through the engine. The data (signed, exponents over +-40 binades) tells
+# the summation orders apart: tests/test_adversarial_host.py asserts that on the CPU. The grids
+# are min(ceil(n / 256), 4096) workgroups of 256 threads, so the grid-stride loops run only past
+# 4096 * 256 elements: the last length of each list.
+COMBINE_STRIDE_N = 4096 * 256 + 257
+
+
+def _combine_on_device(call, parts, n_out, want, what):
+    import gpu_guarded as G
+
+    nparts, n = parts.shape
+    dparts, dy = G.vectors(parts, n), G.result(1, n_out, n_out)  # contiguous partials and y, inside NaN
+    try:
+        _lib.check(call(dparts.ptr, dy.ptr), what)
+        _lib.check(_lib.lib.mvg_stream_sync(None), "sync")
+        G.assert_clean(dy.image(), dy.lay, G.exact_ok(want[None, :]), what)
+        assert not G.violations(dparts.image(), dparts.lay), what  # the partials are overwritten in place only
+    finally:
+        dparts.free()
+        dy.free()
+
+
+@pytest.mark.parametrize("P", [2, 3, 4, 5, 6, 7, 8, 9, 12, 16, 17])
+def test_combine_mpich_on_the_device_is_mpich_reduce(P):
+    # n < pof2; at, just below and just above the 2048-byte switch of algorithm; the fold path
+    # (P not a power of two) on both sides of it
+    import adversarial_cases as AC
+
+    lib = _lib.lib
+    for n in [1, 3, 255, 256, 257, 1000, 70000] + ([COMBINE_STRIDE_N] if P in (4, 5) else []):
+        parts = AC.combine_parts(P, n)
+        want = oracle.mpich_reduce(list(parts))
+        assert np.isfinite(want).all()
+        _combine_on_device(lambda dp, dy: lib.mvg_debug_combine_mpich(dp, P, n, dy, None), parts, n, want,
+                           f"combine_mpich P={P} n={n}")
+    d = mm.DeviceBuffer(8)
+    assert lib.mvg_debug_combine_mpich(d.ptr, 0, 4, d.ptr, None) == _lib.MVG_E_INVALID
+    assert lib.mvg_debug_combine_mpich(d.ptr, 2, -1, d.ptr, None) == _lib.MVG_E_INVALID
+    assert lib.mvg_debug_combine_mpich(None, 2, 4, d.ptr, None) == _lib.MVG_E_INVALID
+    assert lib.mvg_debug_combine_mpich(None, 2, 0, None, None) == _lib.MVG_OK  # nothing to add
+
+
+@pytest.mark.parametrize("gr,gc", [(1, 2), (2, 2), (2, 3), (2, 4), (3, 5)])
+def test_combine_grid_rows_on_the_device_adds_left_to_right_from_zero(gr, gc):
+    import adversarial_cases as AC
+
+    lib = _lib.lib
+    for lr in [1, 3, 257, 1000, 70000] + ([-(-COMBINE_STRIDE_N // gr)] if (gr, gc) == (2, 3) else []):
+        parts = AC.combine_parts(gr * gc, lr, seed=5)
+        want = AC.grid_rows_sum(parts, gr, gc)  # the host's left-to-right sum from 0.0
+        _combine_on_device(lambda dp, dy: lib.mvg_debug_combine_grid_rows(dp, gr, gc, lr, dy, None), parts, gr * lr,
+                           want, f"combine_grid_rows {gr}x{gc} lr={lr}")
+    d = mm.DeviceBuffer(8)
+    assert lib.mvg_debug_combine_grid_rows(d.ptr, 0, 2, 4, d.ptr, None) == _lib.MVG_E_INVALID
+    assert lib.mvg_debug_combine_grid_rows(d.ptr, 2, 2, -1, d.ptr, None) == _lib.MVG_E_INVALID
+    assert lib.mvg_debug_combine_grid_rows(d.ptr, 2, 2, 2, None, None) == _lib.MVG_E_INVALID
+
+
 def _hip_runtime():
     """The HIP runtime libmatvec_gpu.so runs on, through ctypes. PyTorch's wheel ships its own
     libamdhip64 with the same soname (libamdhip64.so.7); the package loads PyTorch first, so the
