@@ -11,9 +11,19 @@ synthetic matrices are regenerated bit-exactly from (seed, R, C).
 
 Usage: python tests/golden/make_golden.py [--only NAME,...]   (needs /root/reference and
 /opt/conda MPICH). --only regenerates just those cases and keeps the others' vectors.
+
+       python tests/golden/make_golden.py --published-sweep
+writes tests/golden/published_sweep.json instead: four sizes of the reference's published sweep
+(test.sh: squares 600...10200, 120...1200 x 60000) at its five process counts 1, 2, 6, 12, 24,
+and of every y only its SHA-256 (as little-endian fp64) and its first and last value in hex.
+P = 24 is past golden.npz's largest P: MPICH folds 8 surplus ranks into 16 before either of its
+MPI_Reduce algorithms, the binomial tree (y <= 2 KiB: 120 and 240 rows) and reduce-scatter +
+gather (600, 1800 rows). Only the runs where the reference is deterministic are recorded: row
+and column split at every P, block split on the 1 x 1 and 1 x 2 grids.
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import os
 import shutil
@@ -54,6 +64,58 @@ CASES = [
     ("big_8192x16384", 8192, 16384, "synth", {"colwise": [4, 8]}),  # R <= C for the column split
 ]
 
+# the reference's published sweep (--published-sweep): name, R, C
+SWEEP_CASES = [("sq_600", 600, 600), ("sq_1800", 1800, 1800), ("wide_120x60000", 120, 60000),
+               ("wide_240x60000", 240, 60000)]
+SWEEP_P = (1, 2, 6, 12, 24)
+SWEEP_PLAN = {"rowwise": SWEEP_P, "colwise": SWEEP_P, "blockwise": (1, 2)}
+
+
+def y_digest(y: np.ndarray) -> dict:
+    """What published_sweep.json keeps of a y: SHA-256 of its little-endian fp64 bytes, and its
+    first and last value as C99 hex floats."""
+    y = np.ascontiguousarray(y, dtype="<f8")
+    return {"sha256": hashlib.sha256(y.tobytes()).hexdigest(), "first": float(y[0]).hex(), "last": float(y[-1]).hex()}
+
+
+def run_reference(work: str, alg: str, p: int, R: int, C: int, what: str) -> np.ndarray:
+    """Rank 0's y of the real reference at p processes on the inputs lying in work/data."""
+    ypath = os.path.join(work, "y.txt")
+    if os.path.exists(ypath):
+        os.remove(ypath)
+    env = dict(os.environ, ORACLE_Y=ypath)
+    cmd = [MPIEXEC, "-n", str(p), os.path.join(REF_BIN, f"multiplier_{alg}"), str(R), str(C)]
+    r = subprocess.run(cmd, cwd=work, env=env, capture_output=True, text=True, timeout=1800)
+    if r.returncode != 0 or not os.path.exists(ypath):
+        raise RuntimeError(f"{what} {alg} P={p} failed: {r.stdout[-500:]} {r.stderr[-500:]}")
+    y = np.loadtxt(ypath, dtype=np.float64, ndmin=1)
+    assert y.shape == (R,), (what, alg, p, y.shape)
+    return y
+
+
+def published_sweep() -> None:
+    runs = []
+    with tempfile.TemporaryDirectory() as work:
+        data = os.path.join(work, "data")
+        os.makedirs(os.path.join(data, "out"))
+        for name, R, C in SWEEP_CASES:
+            write_inputs(data, name, R, C, "synth")
+            for alg, plist in SWEEP_PLAN.items():
+                for p in plist:
+                    y = run_reference(work, alg, p, R, C, name)
+                    runs.append({"name": name, "R": R, "C": C, "alg": alg, "P": p, **y_digest(y)})
+                    print(f"{name:16s} {alg:9s} P={p}: y[0]={y[0]!r} {runs[-1]['sha256'][:16]}", flush=True)
+            for f in os.listdir(data):
+                if f.endswith(".txt"):
+                    os.remove(os.path.join(data, f))
+    meta = {"generator": "tests/golden/make_golden.py --published-sweep",
+            "reference": "oracle/_ref (MPICH 3.3.2, gcc -O0)", "seed_a": 42, "seed_x": 4242,
+            "digest": "sha256 of y as little-endian fp64; first, last: float.hex()", "runs": runs}
+    with open(os.path.join(HERE, "published_sweep.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+        f.write("\n")
+    print(f"wrote {len(runs)} digests")
+
 
 def write_inputs(data_dir: str, name: str, R: int, C: int, source: str) -> None:
     if source == "fixture":
@@ -78,8 +140,14 @@ def main() -> None:
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="", help="comma-separated case names to (re)generate")
-    only = [n for n in ap.parse_args().only.split(",") if n]
+    ap.add_argument("--published-sweep", action="store_true",
+                    help="write published_sweep.json (digests at P up to 24) instead of golden.npz")
+    args = ap.parse_args()
+    only = [n for n in args.only.split(",") if n]
     subprocess.run([os.path.join(REPO, "oracle", "build_ref.sh")], check=True)
+    if args.published_sweep:
+        published_sweep()
+        return
     out: dict[str, np.ndarray] = {}
     manifest = {"generator": "tests/golden/make_golden.py", "reference": "oracle/_ref (MPICH 3.3.2, gcc -O0)",
                 "seed_a": 42, "seed_x": 4242, "cases": []}
@@ -100,16 +168,7 @@ def main() -> None:
             manifest["cases"].append({"name": name, "R": R, "C": C, "source": source, "runs": plan})
             for alg, plist in plan.items():
                 for p in plist:
-                    ypath = os.path.join(work, "y.txt")
-                    if os.path.exists(ypath):
-                        os.remove(ypath)
-                    env = dict(os.environ, ORACLE_Y=ypath)
-                    cmd = [MPIEXEC, "-n", str(p), os.path.join(REF_BIN, f"multiplier_{alg}"), str(R), str(C)]
-                    r = subprocess.run(cmd, cwd=work, env=env, capture_output=True, text=True, timeout=1800)
-                    if r.returncode != 0 or not os.path.exists(ypath):
-                        raise RuntimeError(f"{name} {alg} P={p} failed: {r.stdout[-500:]} {r.stderr[-500:]}")
-                    y = np.loadtxt(ypath, dtype=np.float64, ndmin=1)
-                    assert y.shape == (R,), (name, alg, p, y.shape)
+                    y = run_reference(work, alg, p, R, C, name)
                     out[f"{name}/{alg}/P{p}"] = y
                     print(f"{name:16s} {alg:9s} P={p}: y[0]={y[0]!r}", flush=True)
             for f in os.listdir(data):

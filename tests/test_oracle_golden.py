@@ -135,6 +135,47 @@ def test_oracle_matches_reference_on_config_rows(cfg, alg, R, C, p):
         np.testing.assert_array_equal(y, want)
 
 
+# ---- the reference's published sweep up to its largest P = 24 (tests/golden/make_golden.py
+# --published-sweep): per run the SHA-256 of the real reference's y. At P = 24 MPICH folds 8
+# surplus ranks into 16 before its binomial tree (120 and 240 rows: y <= 2 KiB) and before its
+# reduce-scatter + gather (600, 1800 rows); only deterministic runs are recorded.
+def _sweep_runs():
+    with open(os.path.join(GOLDEN_DIR, "published_sweep.json")) as f:
+        return json.load(f)["runs"]
+
+
+_sweep_inputs = {}
+
+
+@pytest.mark.parametrize("run", _sweep_runs(), ids=lambda r: f"{r['name']}-{r['alg']}-P{r['P']}")
+def test_oracle_hashes_to_the_reference_on_the_published_sweep(run):
+    import hashlib
+
+    R, C = run["R"], run["C"]
+    if (R, C) not in _sweep_inputs:  # computed once per size, left unchanged
+        _sweep_inputs.clear()
+        _sweep_inputs[R, C] = (oracle.synth(R, C, 42), oracle.synth(1, C, 4242)[0])
+    A, x = _sweep_inputs[R, C]
+    y = np.ascontiguousarray(oracle.multiply(run["alg"], A, x, run["P"]), dtype="<f8")
+    assert (float(y[0]).hex(), float(y[-1]).hex()) == (run["first"], run["last"])
+    assert hashlib.sha256(y.tobytes()).hexdigest() == run["sha256"]
+
+
+def test_published_sweep_golden_covers_both_mpich_paths_at_24_ranks():
+    runs = _sweep_runs()
+    have = {(r["R"], r["C"], r["alg"], r["P"]) for r in runs}
+    sizes = [(600, 600), (1800, 1800), (120, 60000), (240, 60000)]
+    want = {(R, C, alg, p) for R, C in sizes for alg in ("rowwise", "colwise") for p in (1, 2, 6, 12, 24)}
+    want |= {(R, C, "blockwise", p) for R, C in sizes for p in (1, 2)}  # the deterministic grids
+    assert have == want and len(runs) == len(want) == 48
+    col24 = [r["R"] * 8 for r in runs if r["alg"] == "colwise" and r["P"] == 24]
+    assert any(b <= 2048 for b in col24) and any(b > 2048 for b in col24)  # binomial tree; reduce-scatter + gather
+    # the column split's order shows in the bits: P = 24 hashes differ from P = 1 at every size
+    by = {(r["R"], r["C"], r["alg"], r["P"]): r["sha256"] for r in runs}
+    assert all(by[R, C, "colwise", 24] != by[R, C, "colwise", 1] for R, C in sizes)
+    assert all(by[R, C, "rowwise", 24] == by[R, C, "rowwise", 1] for R, C in sizes)
+
+
 def test_config_slices_cover_every_baseline_config_and_gpu_count():
     runs = {(cfg, p) for cfg, _, _, _, p in _slice_runs()}
     assert {("cfg2", 1), ("cfg2", 8), ("cfg5", 8)} <= runs
