@@ -357,7 +357,8 @@ int mvg_engine_exact(const mvg_engine* e, int* on);
  * 8 GiB to spare) and rebuilt from the row-major shard by the second multiply after each
  * distribute / fill — a distribution multiplied once never pays for it — and released when exact
  * mode is switched off; MVG_NO_PANELS=1 turns it off. *P = the panel width of local shard i's
- * copy, 0 while it runs the row-major kernels. */
+ * copy, 0 while it runs the row-major kernels: also after a distribute / fill has made a built
+ * copy stale (its memory is kept), until the second multiply rebuilds it. */
 int mvg_engine_exact_panels(const mvg_engine* e, int local_index, int64_t* P);
 /* Chunked distribution (off by default; MVG_OVERLAP=n in the environment sets it at creation):
  * chunks > 1 makes distribute / distribute_shared move each shard's rows in that many chunks on
@@ -366,6 +367,20 @@ int mvg_engine_exact_panels(const mvg_engine* e, int local_index, int64_t* P);
  * per GPU is unchanged). 0 or 1 = one copy, then the GEMV. y is the same either way (row chunks
  * are independent products; bit for bit in exact mode). */
 int mvg_engine_set_overlap(mvg_engine* e, int chunks);
+/* Test hooks of the root-send distribution (one process per GPU: rank 0 stages every peer's
+ * shard through two device buffers and sends it, the reference's sequential root Send loop,
+ * colwise.c:33-57; no device needed by either hook). A shard travels as its x segment, then its
+ * rows in runs of whole rows of at most `stage` doubles, the same list on the sending and the
+ * receiving side. mvg_debug_set_stage_elems: the staging size in doubles that engines created
+ * afterwards use, read once at mvg_engine_create (0 = the default, 256 MiB; n < 0:
+ * MVG_E_INVALID); a live engine keeps the value it was created with. mvg_debug_shard_pieces:
+ * the pieces of rank `rank`'s shard at `stage_elems` doubles (0 = the default), in send order:
+ * row0[i] = -1 for the x segment, else the piece's first shard row; rows[i] whole rows (1 for
+ * the x segment); count[i] doubles. *n pieces are written (none for a shard without columns);
+ * more than `max`, or a shard row longer than the staging, is MVG_E_INVALID. */
+int mvg_debug_set_stage_elems(int64_t n);
+int mvg_debug_shard_pieces(int alg, int64_t R, int64_t C, int nranks, int rank, int64_t stage_elems, int64_t* row0,
+                           int64_t* rows, int64_t* count, int max, int* n);
 
 /* ------------------------------------------------------------------ text I/O (src/matr_utils.c)
  * Same file names under the same directory convention: <dir>/matrix_<R>_<C>.txt,

@@ -168,6 +168,9 @@ SIGNATURES = {
     "mvg_engine_exact": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "mvg_engine_exact_panels": (C.c_int, [_p, C.c_int, C.POINTER(_i64)]),
     "mvg_engine_set_overlap": (C.c_int, [_p, C.c_int]),
+    "mvg_debug_set_stage_elems": (C.c_int, [_i64]),
+    "mvg_debug_shard_pieces": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, _i64, C.POINTER(_i64), C.POINTER(_i64),
+                                         C.POINTER(_i64), C.c_int, C.POINTER(C.c_int)]),
     "mvg_matrix_filename": (C.c_int, [_i64, _i64, C.c_char_p, C.c_size_t]),
     "mvg_vector_filename": (C.c_int, [_i64, C.c_char_p, C.c_size_t]),
     "mvg_load_matr": (C.c_int, [C.c_char_p, _i64, _i64, _p]),

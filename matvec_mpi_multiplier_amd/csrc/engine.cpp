@@ -69,9 +69,12 @@ struct mvg_comm {
 namespace {
 
 constexpr int kRing = 8;
-// Root-send staging: a peer's shard goes out in pieces of at most this many doubles (256 MiB).
-// Sender and receiver cut the pieces with the same function (shard_pieces).
+// Root-send staging: a peer's shard goes out in pieces of at most this many doubles (256 MiB
+// unless mvg_debug_set_stage_elems lowers it). An engine reads the value once, at creation
+// (mvg_engine::stage_elems): the staging allocation, every offset into it and both sides' piece
+// lists (shard_pieces) take it from there, so it cannot change under a live buffer.
 constexpr int64_t kStageElems = (256ll << 20) / (int64_t)sizeof(double);
+int64_t g_stage_elems = kStageElems;  // what the next mvg_engine_create reads
 
 // One rank's streams, events, buffers and communicators. The handles are plain values and
 // free_shard is the one place that releases them: frees need the shard's device current, and
@@ -113,7 +116,7 @@ struct Shard {
     double* dy_row = nullptr;   // block-split row leader: reduced slice (lr doubles)
     double* dy = nullptr;       // rank 0: the full y (R doubles)
     double* gbuf = nullptr;     // rank 0, exact mode: every rank's partial, gathered in rank order
-    // root, one process per GPU (root_send_shards): two staging buffers of kStageElems doubles in
+    // root, one process per GPU (root_send_shards): two staging buffers of stage_elems doubles in
     // one allocation, and the events that order their H2D copies and sends; made on first use
     double* stage = nullptr;
     hipEvent_t copied[2] = {}, sent[2] = {}, ready = nullptr;
@@ -139,6 +142,7 @@ struct mvg_engine {
     int64_t nx = 0;             // multiplies with an exchange issued so far
     bool x_pending = false;     // an exchange may still run (slot (nx - 1) % ring)
     int ring = kRing;           // ring length in use (MVG_XRING, 1 = exchange on the GEMV stream)
+    int64_t stage_elems = kStageElems;  // root-send staging, doubles per buffer (fixed at creation)
     int64_t multiply_calls = 0;
     double kernel_ms_sum = 0.0;
     int64_t kernel_launches = 0;
@@ -398,17 +402,18 @@ int distribute_direct(mvg_engine* e, const double* A, const double* x) {
 
 // ---- root-send: rank 0 holds A and x and sends every peer its shard (one process per GPU)
 // A shard travels as its x segment (row0 = -1), then its rows in runs of whole rows of at
-// most kStageElems doubles. The root's sends and the peer's receives both walk this list, so
-// their counts agree call for call; empty pieces are left out on both sides.
+// most `stage` doubles (the engine's stage_elems). The root's sends and the peer's receives
+// both walk this list, so their counts agree call for call; empty pieces are left out on both
+// sides.
 struct Piece {
     int64_t row0, rows, count;
 };
-int shard_pieces(const mvg_shard& p, std::vector<Piece>* out) {
+int shard_pieces(const mvg_shard& p, int64_t stage, std::vector<Piece>* out) {
     out->clear();
     if (p.n_cols == 0) return MVG_OK;
-    if (p.n_cols > kStageElems) return fail(MVG_E_INVALID, "row larger than staging");
+    if (p.n_cols > stage) return fail(MVG_E_INVALID, "row larger than staging");
     out->push_back({-1, 1, p.n_cols});
-    const int64_t rows_per = kStageElems / p.n_cols;
+    const int64_t rows_per = stage / p.n_cols;
     for (int64_t r0 = 0; r0 < p.n_rows; r0 += rows_per) {
         const int64_t rows = std::min(rows_per, p.n_rows - r0);
         out->push_back({r0, rows, rows * p.n_cols});
@@ -422,7 +427,7 @@ hipEvent_t last_x_done(const mvg_engine* e, const Shard& s) { return s.x_done[(e
 // reference's sequential root Send loop, colwise.c:33-57), overlapping the next piece's H2D
 // with the current piece's send; then copies its own shard.
 int root_send_shards(mvg_engine* e, Shard& s, const double* A, const double* x) {
-    if (!s.stage) MVG_TRY(alloc_doubles(&s.stage, 2 * kStageElems));
+    if (!s.stage) MVG_TRY(alloc_doubles(&s.stage, 2 * e->stage_elems));
     for (hipEvent_t* ev : {&s.copied[0], &s.copied[1], &s.sent[0], &s.sent[1], &s.ready}) MVG_TRY(ensure_event(ev));
     // sent[b] starts recorded on s.stream, behind the previous GEMV (which reads dA, dx)
     // and the caller's exchange wait: every copy_stream write below is ordered after those
@@ -436,9 +441,9 @@ int root_send_shards(mvg_engine* e, Shard& s, const double* A, const double* x) 
     for (int peer = 1; peer < e->nranks; ++peer) {
         mvg_shard p;
         MVG_TRY(mvg_plan_shard(e->alg, e->R, e->C, e->nranks, peer, &p));
-        MVG_TRY(shard_pieces(p, &pieces));
+        MVG_TRY(shard_pieces(p, e->stage_elems, &pieces));
         for (const Piece& pc : pieces) {
-            double* stage = s.stage + buf * kStageElems;
+            double* stage = s.stage + buf * e->stage_elems;
             MVG_HIP(hipStreamWaitEvent(s.copy_stream, s.sent[buf], 0));
             MVG_TRY(pc.row0 < 0 ? h2d_x(stage, p, x, s.copy_stream)
                                 : h2d_rows(stage, p, A, pc.row0, pc.rows, s.copy_stream));
@@ -459,9 +464,9 @@ int root_send_shards(mvg_engine* e, Shard& s, const double* A, const double* x) 
 }
 
 // A peer receives its shard's pieces from rank 0 straight into dx and dA.
-int recv_shard(Shard& s) {
+int recv_shard(const mvg_engine* e, Shard& s) {
     std::vector<Piece> pieces;
-    MVG_TRY(shard_pieces(s.plan, &pieces));
+    MVG_TRY(shard_pieces(s.plan, e->stage_elems, &pieces));
     for (const Piece& pc : pieces)
         MVG_NCCL(ncclRecv(pc.row0 < 0 ? s.dx : s.dA + pc.row0 * s.plan.n_cols, (size_t)pc.count, ncclFloat64, 0, s.world,
                           s.stream));
@@ -885,6 +890,7 @@ int mvg_engine_create(mvg_engine** out, int alg, int64_t R, int64_t C, mvg_comm*
     // forced collectives need an RCCL communicator (a one-device comm made without the
     // variable has none)
     e->always_collect = getenv_flag("MVG_ALWAYS_COLLECT") && comm->locals[0].comm != nullptr;
+    e->stage_elems = g_stage_elems;
     if (const char* v = getenv("MVG_XRING")) e->ring = std::max(1, std::min(kRing, atoi(v)));
     if (const char* ov = getenv("MVG_OVERLAP")) e->overlap_chunks = std::max(0, atoi(ov));
 
@@ -941,7 +947,10 @@ int mvg_engine_set_exact(mvg_engine* e, int on) {
 
 int mvg_engine_exact_panels(const mvg_engine* e, int i, int64_t* P) {
     if (!e || !P || i < 0 || i >= (int)e->shards.size()) return fail(MVG_E_INVALID, "bad index");
-    *P = e->exact && e->shards[i].dAp ? e->shards[i].panelP : 0;
+    // a copy that a write has made stale is kept allocated, but the shard runs the row-major
+    // kernels until the second multiply rebuilds it
+    const Shard& s = e->shards[i];
+    *P = e->exact && s.dAp && s.panels_fresh ? s.panelP : 0;
     return MVG_OK;
 }
 
@@ -1007,7 +1016,7 @@ int mvg_engine_distribute(mvg_engine* e, const double* A, const double* x) {
     // the sends/recvs use the world communicator on s.stream: order them after any exchange
     // still running on s.xstream (one communicator, one order of operations)
     if (e->x_pending) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
-    MVG_TRY(s.rank == 0 ? root_send_shards(e, s, A, x) : recv_shard(s));
+    MVG_TRY(s.rank == 0 ? root_send_shards(e, s, A, x) : recv_shard(e, s));
     e->distributed = true;
     return MVG_OK;
 }
@@ -1112,6 +1121,34 @@ int mvg_engine_collect(mvg_engine* e, double* y) {
             MVG_HIP(hipMemcpyAsync(y, s.dy, (size_t)e->R * sizeof(double), hipMemcpyDeviceToHost, s.stream));
         MVG_HIP(hipStreamSynchronize(s.stream));
     }
+    return MVG_OK;
+}
+
+// Test hooks of the root-send staging (no device needed). The staging size that engines created
+// from now on use (0: the default), and the pieces shard_pieces cuts one rank's shard into at a
+// given staging size: what root_send_shards sends that rank and recv_shard receives there.
+int mvg_debug_set_stage_elems(int64_t n) {
+    if (n < 0) return fail(MVG_E_INVALID, "mvg_debug_set_stage_elems: negative size");
+    g_stage_elems = n == 0 ? kStageElems : n;
+    return MVG_OK;
+}
+
+int mvg_debug_shard_pieces(int alg, int64_t R, int64_t C, int nranks, int rank, int64_t stage_elems, int64_t* row0,
+                           int64_t* rows, int64_t* count, int max, int* n) {
+    if (!n || max < 0 || stage_elems < 0 || (max > 0 && (!row0 || !rows || !count)))
+        return fail(MVG_E_INVALID, "mvg_debug_shard_pieces: bad arguments");
+    *n = 0;
+    mvg_shard p;
+    MVG_TRY(mvg_plan_shard(alg, R, C, nranks, rank, &p));
+    std::vector<Piece> pieces;
+    MVG_TRY(shard_pieces(p, stage_elems == 0 ? kStageElems : stage_elems, &pieces));
+    if ((int64_t)pieces.size() > max) return fail(MVG_E_INVALID, "mvg_debug_shard_pieces: piece buffer too small");
+    for (size_t i = 0; i < pieces.size(); ++i) {
+        row0[i] = pieces[i].row0;
+        rows[i] = pieces[i].rows;
+        count[i] = pieces[i].count;
+    }
+    *n = (int)pieces.size();
     return MVG_OK;
 }
 
