@@ -141,6 +141,14 @@ typedef struct mvg_xcall {
 } mvg_xcall;
 int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, mvg_xcall* calls, int max_calls,
                              int* ncalls);
+/* The same for one mvg_engine_multiply_multi over a block of nv vectors (1 .. MVG_MAX_VECTORS):
+ * one group per step as above; a reduce is one call of count * nv doubles (the block's buffers
+ * are column-major, one vector per column), a gather nv calls of count doubles per member, vector
+ * v in call v of the member (into column v of the root's Y); exact mode: nv rank-order gathers per
+ * rank in one group, then nv combines on rank 0 (blockwise.c:144-210 / colwise.c:124 per vector;
+ * rowwise.c:141's gather is exact as it is). */
+int mvg_debug_trace_exchange_multi(int alg, int64_t R, int64_t C, int ndev, int exact, int nv, mvg_xcall* calls,
+                                   int max_calls, int* ncalls);
 
 /* ------------------------------------------------------------------ synthetic inputs
  * value(seed, idx) = (double)k / 10000.0, k = floor(splitmix64(s0 + idx*gamma) * 10000 / 2^64),
@@ -239,6 +247,25 @@ int mvg_gemv_exact_variant(const double* d_A, int64_t lda, const double* d_x, do
 int mvg_gemv_exact_variant_count(void);
 int mvg_gemv_exact_auto_variant(int64_t lda, int64_t m, int64_t k);
 const char* mvg_gemv_exact_variant_name(int variant);
+/* Bit-exact form of mvg_gemv_multi (same layout and argument rules: vector v at d_X + v*ldx and
+ * d_Y + v*ldy, ldx >= k, ldy >= m, any nv >= 0; m == 0 or nv == 0 is a no-op, k == 0 writes
+ * zeros): column v of Y is bit-identical to mvg_gemv_exact on x_v, i.e. to multiply_std_rowwise
+ * (src/matr_utils.c:86-96) per vector. The multi kernels carry 2 or 4 independent chains per
+ * row over one read of A (csrc/gemv_exact.hip, gemv_seq_hop_multi); the vectors go out in groups
+ * of the variant's chain count, a last single vector through mvg_gemv_exact. Any lda, ldx and
+ * alignment. The automatic choice takes a multi kernel only where a committed sweep showed it
+ * faster than separate passes, and separate mvg_gemv_exact passes everywhere else. */
+int mvg_gemv_exact_multi(const double* d_A, int64_t lda, const double* d_X, int64_t ldx, double* d_Y, int64_t ldy,
+                         int64_t m, int64_t k, int nv, void* stream);
+/* explicit variant (0 = auto; names via mvg_gemv_exact_multi_variant_name: "separate" = one
+ * mvg_gemv_exact per vector, hopm_l<L>_w<W>_u<U>_v<NV> = NV chains per row, L lanes per row
+ * holding W columns each, U segments in flight) */
+int mvg_gemv_exact_multi_variant(const double* d_A, int64_t lda, const double* d_X, int64_t ldx, double* d_Y,
+                                 int64_t ldy, int64_t m, int64_t k, int nv, int variant, void* stream);
+int mvg_gemv_exact_multi_variant_count(void);
+/* the variant mvg_gemv_exact_multi picks for nv >= 2 vectors; 0 for nv < 2 (mvg_gemv_exact) */
+int mvg_gemv_exact_multi_auto_variant(int64_t lda, int64_t ldx, int64_t m, int64_t k, int nv);
+const char* mvg_gemv_exact_multi_variant_name(int variant);
 /* Test hooks of the exact dispatch (no counterpart in the reference). mvg_debug_set_cu_count:
  * the CU count the dispatch plans whole rounds of workgroups for (0 = the current device's).
  * mvg_debug_set_exact_even_lds: the LDS reservation of the evenly placed form in bytes (0 = its
@@ -367,6 +394,36 @@ int mvg_engine_exact_panels(const mvg_engine* e, int local_index, int64_t* P);
  * per GPU is unchanged). 0 or 1 = one copy, then the GEMV. y is the same either way (row chunks
  * are independent products; bit for bit in exact mode). */
 int mvg_engine_set_overlap(mvg_engine* e, int chunks);
+/* A block of vectors on the distributed A (beyond the reference, whose drivers know one x):
+ * Y = A X for X = [x_0 ... x_{nv-1}], 1 <= nv <= MVG_MAX_VECTORS, with one pass over each shard
+ * and one exchange for the whole block. Per vector the result is what distribute's x gets from
+ * multiply: multiply_std_rowwise on the shard (matr_utils.c:86-96), then the row split's gather
+ * (rowwise.c:141), the column split's reduce (colwise.c:124) or the block split's row sums
+ * (blockwise.c:144-210). In exact mode column v of Y is bit-identical to the exact single-vector
+ * y for x_v (every vector combined as if alone: MPICH's algorithm switch looks at one y's
+ * length); in tree mode it is within 1e-12 relative of it on non-negative data.
+ *   set_vectors        : the root's host X (C x nv column-major, vector v at X_host + v*ldx,
+ *                        ldx >= C; NULL off the root with one process per GPU) -> the whole X on
+ *                        every device (H2D per device, or the root's H2D and an ncclBroadcast).
+ *                        Touches neither A nor the single x, and needs no earlier distribute.
+ *                        The block's device buffers are made here and remade when nv grows. Like
+ *                        every write on the GEMV stream it drops an open kernel-timing span.
+ *   fill_synth_vectors : X generated on each device, X[j, v] = mvg_synth_value(seed_x, v*C + j).
+ *   multiply_multi     : mvg_gemv_multi (mvg_gemv_exact_multi in exact mode) on the row-major
+ *                        shard, then the block's exchange; needs A (distribute / fill_synth) and
+ *                        X, MVG_E_STATE otherwise. Asynchronous like multiply. It is never part
+ *                        of kernel timing (an open span is dropped) and does not count as a
+ *                        multiply for exact mode's panel copy.
+ *   collect_multi      : Y (R x nv column-major, ldy >= R) -> host on the root.
+ *   vectors            : nv of the block last set (0: none yet).
+ * The block has its own device buffers: collect after a multiply_multi still returns the last
+ * multiply's y, and collect_multi after a multiply the last multiply_multi's Y. */
+#define MVG_MAX_VECTORS 16
+int mvg_engine_set_vectors(mvg_engine* e, const double* X_host, int64_t ldx, int nv);
+int mvg_engine_fill_synth_vectors(mvg_engine* e, uint64_t seed_x, int nv);
+int mvg_engine_multiply_multi(mvg_engine* e);
+int mvg_engine_collect_multi(mvg_engine* e, double* Y_host, int64_t ldy);
+int mvg_engine_vectors(const mvg_engine* e, int* nv);
 /* Test hooks of the root-send distribution (one process per GPU: rank 0 stages every peer's
  * shard through two device buffers and sends it, the reference's sequential root Send loop,
  * colwise.c:33-57; no device needed by either hook). A shard travels as its x segment, then its

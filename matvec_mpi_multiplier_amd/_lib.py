@@ -85,6 +85,7 @@ X_WORLD, X_ROW, X_COL = 0, 1, 2
 X_BUF_PART, X_BUF_ROW, X_BUF_Y, X_BUF_GATHERED = 0, 1, 2, 3
 XCALL_SPLIT, XCALL_GATHER, XCALL_REDUCE, XCALL_COMBINE = 0, 1, 2, 3
 MAX_XSTEPS = 4
+MAX_VECTORS = 16
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -130,9 +131,16 @@ SIGNATURES = {
     "mvg_gemv_exact_variant": (C.c_int, [_p, _i64, _p, _p, _i64, _i64, C.c_int, _p]),
     "mvg_gemv_exact_variant_count": (C.c_int, []),
     "mvg_gemv_exact_auto_variant": (C.c_int, [_i64, _i64, _i64]),
+    "mvg_gemv_exact_multi": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, C.c_int, _p]),
+    "mvg_gemv_exact_multi_variant": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, C.c_int, C.c_int, _p]),
+    "mvg_gemv_exact_multi_variant_count": (C.c_int, []),
+    "mvg_gemv_exact_multi_auto_variant": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int]),
+    "mvg_gemv_exact_multi_variant_name": (C.c_char_p, [C.c_int]),
     "mvg_debug_set_cu_count": (C.c_int, [C.c_int]),
     "mvg_debug_trace_exchange": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, C.POINTER(XCall), C.c_int,
                                            C.POINTER(C.c_int)]),
+    "mvg_debug_trace_exchange_multi": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(XCall),
+                                                 C.c_int, C.POINTER(C.c_int)]),
     "mvg_debug_set_exact_even_lds": (C.c_int, [_i64]),
     "mvg_gemv_exact_even_refused": (C.c_int, [C.c_int]),
     "mvg_debug_combine_mpich": (C.c_int, [_p, C.c_int, _i64, _p, _p]),
@@ -168,6 +176,11 @@ SIGNATURES = {
     "mvg_engine_exact": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "mvg_engine_exact_panels": (C.c_int, [_p, C.c_int, C.POINTER(_i64)]),
     "mvg_engine_set_overlap": (C.c_int, [_p, C.c_int]),
+    "mvg_engine_set_vectors": (C.c_int, [_p, _p, _i64, C.c_int]),
+    "mvg_engine_fill_synth_vectors": (C.c_int, [_p, C.c_uint64, C.c_int]),
+    "mvg_engine_multiply_multi": (C.c_int, [_p]),
+    "mvg_engine_collect_multi": (C.c_int, [_p, _p, _i64]),
+    "mvg_engine_vectors": (C.c_int, [_p, C.POINTER(C.c_int)]),
     "mvg_debug_set_stage_elems": (C.c_int, [_i64]),
     "mvg_debug_shard_pieces": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, _i64, C.POINTER(_i64), C.POINTER(_i64),
                                          C.POINTER(_i64), C.c_int, C.POINTER(C.c_int)]),

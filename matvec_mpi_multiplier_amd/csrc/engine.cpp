@@ -116,6 +116,16 @@ struct Shard {
     double* dy_row = nullptr;   // block-split row leader: reduced slice (lr doubles)
     double* dy = nullptr;       // rank 0: the full y (R doubles)
     double* gbuf = nullptr;     // rank 0, exact mode: every rank's partial, gathered in rank order
+    // a block of vectors (mvg_engine_set_vectors): the whole X (C x nv, ld = C) on every rank, and
+    // exchange buffers of nv columns, their own so that the single vector's y and its ring stay
+    // what the last mvg_engine_multiply left: the ring of partials (ld = y_len), the grid-row
+    // buffer (ld = y_len), rank 0's Y (ld = R) and exact mode's gather buffer (vector v's P
+    // partials at v * P * y_len; made by the first exact mvg_engine_multiply_multi)
+    double* dX = nullptr;
+    double* dY_parts[kRing] = {};
+    double* dY_row = nullptr;
+    double* dY = nullptr;
+    double* gbuf_multi = nullptr;
     // root, one process per GPU (root_send_shards): two staging buffers of stage_elems doubles in
     // one allocation, and the events that order their H2D copies and sends; made on first use
     double* stage = nullptr;
@@ -143,6 +153,8 @@ struct mvg_engine {
     bool x_pending = false;     // an exchange may still run (slot (nx - 1) % ring)
     int ring = kRing;           // ring length in use (MVG_XRING, 1 = exchange on the GEMV stream)
     int64_t stage_elems = kStageElems;  // root-send staging, doubles per buffer (fixed at creation)
+    int nv = 0;      // vectors of the block last set (0: none yet)
+    int nv_cap = 0;  // vectors the block's buffers hold
     int64_t multiply_calls = 0;
     double kernel_ms_sum = 0.0;
     int64_t kernel_launches = 0;
@@ -165,6 +177,8 @@ struct XOps {
     virtual ncclResult_t collective(int op, const double* src, double* dst, size_t count, int root, ncclComm_t comm,
                                     hipStream_t st) = 0;
     virtual int combine(const mvg_engine* e, const Shard& s, hipStream_t st) = 0;
+    // the same combine for one vector of a block: rank 0's gathered partials of it -> its y
+    virtual int combine_vector(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t st) = 0;
 };
 
 struct DeviceXOps final : XOps {
@@ -183,6 +197,11 @@ struct DeviceXOps final : XOps {
         return e->alg == MVG_ALG_COLWISE ? launch_combine_mpich_reduce(s.gbuf, e->nranks, e->R, s.dy, st)
                                          : launch_combine_grid_rows(s.gbuf, s.plan.grid_rows, s.plan.grid_cols,
                                                                     s.plan.y_len, s.dy, st);
+    }
+    int combine_vector(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t st) override {
+        return e->alg == MVG_ALG_COLWISE ? launch_combine_mpich_reduce(parts, e->nranks, e->R, y, st)
+                                         : launch_combine_grid_rows(parts, s.plan.grid_rows, s.plan.grid_cols,
+                                                                    s.plan.y_len, y, st);
     }
 };
 
@@ -285,10 +304,24 @@ int alloc_doubles(double** p, int64_t n) {
     return MVG_E_NOMEM;
 }
 
+// The block-of-vectors buffers of a shard (its device current, nothing in flight on them):
+// free_shard, and make_vector_buffers when the block grows.
+void release_vector_buffers(Shard& s) {
+    for (double** p : {&s.dX, &s.dY_row, &s.dY, &s.gbuf_multi}) {
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+    for (int b = 0; b < kRing; ++b) {
+        if (s.dY_parts[b]) (void)hipFree(s.dY_parts[b]);
+        s.dY_parts[b] = nullptr;
+    }
+}
+
 void free_shard(Shard& s) {
     (void)hipSetDevice(s.device);
     for (hipStream_t st : {s.stream, s.copy_stream, s.xstream})
         if (st) (void)hipStreamSynchronize(st);
+    release_vector_buffers(s);
     for (double* p : {s.dA, s.dAp, s.dx, s.dy_row, s.dy, s.stage, s.gbuf})
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> events = {s.span_t0, s.span_t1, s.copy_ready, s.copied[0], s.copied[1],
@@ -513,6 +546,63 @@ int exchange(mvg_engine* e, int b, bool serial, XOps& ops) {
     return e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact(e, b, serial, ops) : exchange_plan(e, b, serial, ops);
 }
 
+// ---- the same exchange for a block of nv vectors (mvg_engine_multiply_multi), out of slot b of
+// the block's ring. Every buffer is column-major, one vector per column: a reduce step moves the
+// nv columns as one contiguous run of count * nv doubles; a gather step moves vector v with its
+// own call inside the step's one group, into column v of the root's Y (ld = R: the members'
+// pieces of one vector make up a whole y), so Y needs no transposing pass.
+int exchange_plan_multi(mvg_engine* e, int b, bool serial, int nv, XOps& ops) {
+    for (int k = 0; k < e->shards[0].nsteps; ++k) {
+        const char* what = e->shards[0].steps[k].op == MVG_X_GATHER ? "ncclGather" : "ncclReduce";
+        MVG_TRY(grouped(e->shards, ops, what, [&](Shard& s) {
+            const mvg_xstep& st = s.steps[k];
+            if (!st.member) return ncclSuccess;
+            ops.set_device(s.device);
+            double* bufs[3] = {s.dY_parts[b], s.dY_row, s.dY};  // by MVG_X_BUF_*
+            const bool writes = bufs[st.dst] != nullptr;  // recvbuff is only written on the root
+            double* dst = writes ? bufs[st.dst] : s.dY_parts[b];
+            hipStream_t stream = serial ? s.stream : s.xstream;
+            if (st.op == MVG_X_REDUCE)
+                return ops.collective(st.op, bufs[st.src], dst, (size_t)st.count * nv, st.root, s.xcomm[k], stream);
+            ncclResult_t r = ncclSuccess;
+            for (int v = 0; v < nv && r == ncclSuccess; ++v)
+                r = ops.collective(st.op, bufs[st.src] + v * st.count, writes ? dst + v * e->R : dst, (size_t)st.count,
+                                   st.root, s.xcomm[k], stream);
+            return r;
+        }));
+    }
+    return MVG_OK;
+}
+
+// Exact mode: per vector the rank-order gather of exchange_exact (all nv in one group), then the
+// reference's combine once per vector, each as if that vector were alone (the MPICH algorithm
+// switch looks at one y's length).
+int exchange_exact_multi(mvg_engine* e, int b, bool serial, int nv, XOps& ops) {
+    MVG_TRY(grouped(e->shards, ops, "ncclGather (exact)", [&](Shard& s) {
+        ops.set_device(s.device);
+        const int64_t n = s.plan.y_len;
+        ncclResult_t r = ncclSuccess;
+        for (int v = 0; v < nv && r == ncclSuccess; ++v)
+            r = ops.collective(MVG_X_GATHER, s.dY_parts[b] + v * n,
+                               s.rank == 0 ? s.gbuf_multi + v * e->nranks * n : s.dY_parts[b], (size_t)n, 0, s.world,
+                               serial ? s.stream : s.xstream);
+        return r;
+    }));
+    for (auto& s : e->shards) {
+        if (s.rank != 0) continue;
+        ops.set_device(s.device);
+        for (int v = 0; v < nv; ++v)
+            MVG_TRY(ops.combine_vector(e, s, s.gbuf_multi + v * e->nranks * s.plan.y_len, s.dY + v * e->R,
+                                       serial ? s.stream : s.xstream));
+    }
+    return MVG_OK;
+}
+
+int exchange_multi(mvg_engine* e, int b, bool serial, int nv, XOps& ops) {
+    return e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact_multi(e, b, serial, nv, ops)
+                                                 : exchange_plan_multi(e, b, serial, nv, ops);
+}
+
 // The recorder behind mvg_debug_trace_exchange. Communicators and buffers are stand-in handles
 // the trace hands out; every call is listed with the group it was issued in.
 struct TraceXOps final : XOps {
@@ -527,9 +617,10 @@ struct TraceXOps final : XOps {
             if (kv.first == (uintptr_t)c) return kv.second;
         return -2;
     }
-    int buf_of(const double* p) const {
+    static constexpr uintptr_t kBufSpan = (uintptr_t)1 << 40;  // bytes a stand-in buffer spans
+    int buf_of(const double* p) const {  // a vector's part of a block's buffer is an offset into it
         for (auto& kv : buffers)
-            if (kv.first == (uintptr_t)p) return kv.second.second;
+            if ((uintptr_t)p >= kv.first && (uintptr_t)p - kv.first < kBufSpan) return kv.second.second;
         return -1;
     }
     mvg_xcall base(int kind) const {
@@ -577,6 +668,14 @@ struct TraceXOps final : XOps {
         c.count = s.plan.y_len * e->nranks;
         c.src = buf_of(s.gbuf);
         c.dst = buf_of(s.dy);
+        calls.push_back(c);
+        return MVG_OK;
+    }
+    int combine_vector(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t) override {
+        mvg_xcall c = base(MVG_XCALL_COMBINE);
+        c.count = s.plan.y_len * e->nranks;
+        c.src = buf_of(parts);
+        c.dst = buf_of(y);
         calls.push_back(c);
         return MVG_OK;
     }
@@ -1124,6 +1223,150 @@ int mvg_engine_collect(mvg_engine* e, double* y) {
     return MVG_OK;
 }
 
+// ------------------------------------------------------------------ a block of vectors
+// Y = A X for X = [x_0 ... x_{nv-1}] on the distributed A: per vector what distribute's x gets
+// from multiply — matr_utils.c:86-96 on the shard, then rowwise.c:141, colwise.c:124 or
+// blockwise.c:144-210 — with one pass over the shard and one exchange for the whole block.
+namespace {
+
+// The block's buffers on every local shard, for at least nv vectors: made by the first
+// set_vectors / fill_synth_vectors and remade when nv grows. Nothing may still read the old
+// ones: the shard's streams are drained first.
+int make_vector_buffers(mvg_engine* e, int nv) {
+    if (nv <= e->nv_cap) return MVG_OK;
+    e->nv_cap = e->nv = 0;
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        MVG_HIP(hipStreamSynchronize(s.stream));
+        if (s.xstream) MVG_HIP(hipStreamSynchronize(s.xstream));
+        release_vector_buffers(s);
+        const XBufLens xb = exchange_buffers(*e, s, false);
+        MVG_TRY(alloc_doubles(&s.dX, e->C * nv));
+        if (s.nsteps > 0)  // alone (no exchange) the product goes straight into Y
+            for (int b = 0; b < e->ring; ++b) MVG_TRY(alloc_doubles(&s.dY_parts[b], xb.len[MVG_X_BUF_PART] * nv));
+        MVG_TRY(alloc_doubles(&s.dY_row, xb.len[MVG_X_BUF_ROW] * nv));
+        MVG_TRY(alloc_doubles(&s.dY, xb.len[MVG_X_BUF_Y] * nv));
+    }
+    e->nv_cap = nv;
+    return MVG_OK;
+}
+
+// set_vectors and fill_synth_vectors write dX on the GEMV stream: inside an open kernel-timing
+// span that is no longer GEMVs alone.
+int begin_vectors(mvg_engine* e, int nv, const char* who) {
+    if (!e) return fail(MVG_E_INVALID, "null engine");
+    if (nv < 1 || nv > MVG_MAX_VECTORS) return fail(MVG_E_INVALID, std::string(who) + ": nv outside 1 .. MVG_MAX_VECTORS");
+    if (span_is_open(e)) e->span_valid = false;
+    return MVG_OK;
+}
+
+}  // namespace
+
+int mvg_engine_set_vectors(mvg_engine* e, const double* X, int64_t ldx, int nv) {
+    MVG_TRY(begin_vectors(e, nv, "mvg_engine_set_vectors"));
+    bool root = false;
+    for (auto& s : e->shards) root |= s.rank == 0;
+    if (root && e->C > 0 && (!X || ldx < e->C)) return fail(MVG_E_INVALID, "mvg_engine_set_vectors: root needs X with ldx >= C");
+    DeviceGuard g;
+    MVG_TRY(make_vector_buffers(e, nv));
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        if (e->single_process) {  // every device pulls the whole X itself
+            MVG_TRY(h2d_region(s.dX, X, ldx, nv, e->C, s.stream));
+            continue;
+        }
+        // one process per GPU: the root's copy, then a broadcast on the world communicator, in
+        // order behind any exchange still running on it (as the root-send distribution)
+        if (e->x_pending) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+        if (s.rank == 0) MVG_TRY(h2d_region(s.dX, X, ldx, nv, e->C, s.stream));
+        if (e->C > 0) MVG_NCCL(ncclBroadcast(s.dX, s.dX, (size_t)e->C * nv, ncclFloat64, 0, s.world, s.stream));
+    }
+    e->nv = nv;
+    return MVG_OK;
+}
+
+int mvg_engine_fill_synth_vectors(mvg_engine* e, uint64_t seed_x, int nv) {
+    MVG_TRY(begin_vectors(e, nv, "mvg_engine_fill_synth_vectors"));
+    DeviceGuard g;
+    MVG_TRY(make_vector_buffers(e, nv));
+    for (auto& s : e->shards) {  // X as nv rows of C: element (v, j) is index v * C + j
+        MVG_HIP(hipSetDevice(s.device));
+        MVG_TRY(mvg_synth_fill_device(s.dX, e->C, nv, e->C, 0, 0, e->C, seed_x, s.stream));
+    }
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        MVG_HIP(hipStreamSynchronize(s.stream));
+    }
+    e->nv = nv;
+    return MVG_OK;
+}
+
+int mvg_engine_vectors(const mvg_engine* e, int* nv) {
+    if (!e || !nv) return fail(MVG_E_INVALID, "null");
+    *nv = e->nv;
+    return MVG_OK;
+}
+
+// Always on the row-major shard (never the panel copy), never timed, and no "use" of A for the
+// panel copy's second-multiply rule. The block's ring shares the single vector's slot counter
+// and events: one order of exchanges on the exchange stream, so the once-per-ring wait, x_pending
+// and the collects' waits cover both kinds of multiply.
+int mvg_engine_multiply_multi(mvg_engine* e) {
+    if (!e) return fail(MVG_E_INVALID, "null engine");
+    if (!e->distributed || e->nv == 0)
+        return fail(MVG_E_STATE, "mvg_engine_multiply_multi needs distribute/fill and set_vectors/fill_synth_vectors first");
+    DeviceGuard g;
+    if (span_is_open(e)) e->span_valid = false;  // not a GEMV of the span
+    const int nv = e->nv;
+    const bool solo = e->shards[0].nsteps == 0;
+    const bool serial = e->ring == 1;
+    const int b = solo ? 0 : (int)(e->nx % e->ring);
+    const bool wait_ring = !solo && !serial && e->x_pending && b == 0;
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        if (wait_ring) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+        MVG_TRY(drain_chunks(s));  // a chunked distribution still copying: wait, then multiply whole
+        const mvg_shard& p = s.plan;
+        if (e->exact && !solo && e->alg != MVG_ALG_ROWWISE && s.rank == 0 && !s.gbuf_multi)
+            MVG_TRY(alloc_doubles(&s.gbuf_multi, exchange_buffers(*e, s, true).len[MVG_X_BUF_GATHERED] * e->nv_cap));
+        const double* X = s.dX ? s.dX + p.col_off : nullptr;
+        double* out = solo ? s.dY : s.dY_parts[b];
+        MVG_TRY(e->exact ? mvg_gemv_exact_multi(s.dA, p.n_cols, X, e->C, out, p.y_len, p.n_rows, p.n_cols, nv, s.stream)
+                         : mvg_gemv_multi(s.dA, p.n_cols, X, e->C, out, p.y_len, p.n_rows, p.n_cols, nv, s.stream));
+        if (!solo && !serial) {
+            MVG_HIP(hipEventRecord(s.gemv_done[b], s.stream));
+            MVG_HIP(hipStreamWaitEvent(s.xstream, s.gemv_done[b], 0));
+        }
+    }
+    if (solo) return MVG_OK;
+    MVG_TRY(exchange_multi(e, b, serial, nv, g_device_ops));
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        if (!serial) MVG_HIP(hipEventRecord(s.x_done[b], s.xstream));
+    }
+    e->x_pending = !serial;
+    ++e->nx;
+    return MVG_OK;
+}
+
+int mvg_engine_collect_multi(mvg_engine* e, double* Y, int64_t ldy) {
+    if (!e) return fail(MVG_E_INVALID, "null engine");
+    if (e->nv == 0) return fail(MVG_E_STATE, "mvg_engine_collect_multi before set_vectors/fill_synth_vectors");
+    DeviceGuard g;
+    for (auto& s : e->shards) {
+        if (s.rank != 0) continue;
+        if (!Y || ldy < e->R) return fail(MVG_E_INVALID, "root needs a Y buffer with ldy >= R");
+        MVG_HIP(hipSetDevice(s.device));
+        if (e->x_pending)  // Y is complete once the last exchange is
+            MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+        if (e->R > 0)
+            MVG_HIP(hipMemcpy2DAsync(Y, (size_t)ldy * sizeof(double), s.dY, (size_t)e->R * sizeof(double),
+                                     (size_t)e->R * sizeof(double), (size_t)e->nv, hipMemcpyDeviceToHost, s.stream));
+        MVG_HIP(hipStreamSynchronize(s.stream));
+    }
+    return MVG_OK;
+}
+
 // Test hooks of the root-send staging (no device needed). The staging size that engines created
 // from now on use (0: the default), and the pieces shard_pieces cuts one rank's shard into at a
 // given staging size: what root_send_shards sends that rank and recv_shard receives there.
@@ -1156,9 +1399,11 @@ int mvg_debug_shard_pieces(int alg, int64_t R, int64_t C, int nranks, int rank, 
 // the shards the engine would create over G local devices (the same planner, the same buffer
 // choices), their communicator splits and one multiply's exchange, issued through the recorder
 // instead of RCCL (exchange_buffers, split_steps, exchange: the engine's own code).
-int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, mvg_xcall* calls, int max_calls,
-                             int* ncalls) {
-    if (!calls || !ncalls || ndev <= 0 || max_calls < 0) return fail(MVG_E_INVALID, "mvg_debug_trace_exchange: bad arguments");
+// nv = 0: one multiply's exchange; nv >= 1: one multiply_multi's over a block of nv vectors.
+static int trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, int nv, mvg_xcall* calls, int max_calls,
+                          int* ncalls) {
+    if (!calls || !ncalls || ndev <= 0 || max_calls < 0 || nv < 0 || nv > MVG_MAX_VECTORS)
+        return fail(MVG_E_INVALID, "mvg_debug_trace_exchange: bad arguments");
     *ncalls = 0;
     mvg_engine e;
     e.alg = alg;
@@ -1170,7 +1415,7 @@ int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact,
     e.shards.resize(ndev);
     TraceXOps ops;
     auto fake = [&](int r, int id) {
-        const uintptr_t a = ((uintptr_t)(r + 1) << 24) + ((uintptr_t)(id + 1) << 16);
+        const uintptr_t a = ((uintptr_t)(r + 1) << 44) + (uintptr_t)(id + 1) * TraceXOps::kBufSpan;
         ops.buffers.push_back({a, {r, id}});
         return (double*)a;
     };
@@ -1183,16 +1428,29 @@ int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact,
         MVG_TRY(mvg_plan_shard(alg, R, C, ndev, r, &s.plan));
         MVG_TRY(mvg_plan_exchange(alg, R, C, ndev, r, 0, s.steps, MVG_MAX_XSTEPS, &s.nsteps));
         const XBufLens xb = exchange_buffers(e, s, e.exact);
-        double** slot[4] = {&s.dy_parts[0], &s.dy_row, &s.dy, &s.gbuf};  // by MVG_X_BUF_*
+        double** single[4] = {&s.dy_parts[0], &s.dy_row, &s.dy, &s.gbuf};  // by MVG_X_BUF_*
+        double** block[4] = {&s.dY_parts[0], &s.dY_row, &s.dY, &s.gbuf_multi};
+        double*** slot = nv > 0 ? block : single;
         for (int id = 0; id < 4; ++id)
             if (xb.len[id] >= 0) *slot[id] = fake(r, id);
     }
     MVG_TRY(split_steps(e.shards, ops));
-    if (e.shards[0].nsteps > 0) MVG_TRY(exchange(&e, 0, false, ops));
+    if (e.shards[0].nsteps > 0) MVG_TRY(nv > 0 ? exchange_multi(&e, 0, false, nv, ops) : exchange(&e, 0, false, ops));
     if ((int)ops.calls.size() > max_calls) return fail(MVG_E_INVALID, "mvg_debug_trace_exchange: calls buffer too small");
     for (size_t i = 0; i < ops.calls.size(); ++i) calls[i] = ops.calls[i];
     *ncalls = (int)ops.calls.size();
     return MVG_OK;
+}
+
+int mvg_debug_trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, mvg_xcall* calls, int max_calls,
+                             int* ncalls) {
+    return trace_exchange(alg, R, C, ndev, exact, 0, calls, max_calls, ncalls);
+}
+
+int mvg_debug_trace_exchange_multi(int alg, int64_t R, int64_t C, int ndev, int exact, int nv, mvg_xcall* calls,
+                                   int max_calls, int* ncalls) {
+    if (nv < 1) return fail(MVG_E_INVALID, "mvg_debug_trace_exchange_multi: nv outside 1 .. MVG_MAX_VECTORS");
+    return trace_exchange(alg, R, C, ndev, exact, nv, calls, max_calls, ncalls);
 }
 
 }  // extern "C"

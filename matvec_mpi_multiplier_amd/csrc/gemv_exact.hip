@@ -461,6 +461,146 @@ __global__ __launch_bounds__(64 * NW) void gemv_seq_hop_xl(const double* __restr
 }
 constexpr int64_t kXlMaxK = 8192;  // x in LDS: up to 64 KiB per workgroup
 
+// ------------------------------------------------------------------ several vectors per pass
+// gemv_seq_hop with NV independent chains per row (mvg_gemv_exact_multi): a lane loads its W
+// columns of A once per segment and its W entries of each of the NV vectors, forms NV sets of W
+// rounded products and advances NV running sums, every one of them the single-vector chain
+// (matr_utils.c:86-96 per vector): same column order, same hops, same alternating direction, so
+// column v of Y has the bits of gemv_seq_hop on x_v. The chains are independent, so their adds
+// interleave in the VALU while the A bytes are paid for once. These are siblings of hop_segment /
+// hop_masked_segment / hop_chain, not generalisations: the single-vector instantiations keep the
+// code, and the register allocation, they had.
+template <int L, int W, int NV, bool FWD>
+__device__ __forceinline__ void hop_segment_multi(double (&sum)[NV], const dbl2x (&a)[W / 2],
+                                                  const dbl2x (&xv)[NV][W / 2]) {
+    double p[NV][W];
+#pragma unroll
+    for (int n = 0; n < NV; ++n)
+#pragma unroll
+        for (int v = 0; v < W / 2; ++v) p[n][2 * v] = a[v].x * xv[n][v].x, p[n][2 * v + 1] = a[v].y * xv[n][v].y;
+#pragma unroll
+    for (int t = 0; t < L; ++t) {
+#pragma unroll
+        for (int j = 0; j < W; ++j)
+#pragma unroll
+            for (int n = 0; n < NV; ++n) sum[n] = sum[n] + p[n][j];
+        if (t + 1 < L)
+#pragma unroll
+            for (int n = 0; n < NV; ++n) sum[n] = hop<L, FWD>(sum[n]);
+    }
+}
+
+// hop_masked_segment for NV chains: columns outside [lo, hi) are 0 x 0 = +0.0 in every chain.
+// xs[n]: vector n.
+template <int L, int W, int NV>
+__device__ __forceinline__ void hop_masked_segment_multi(double (&sum)[NV], const double* __restrict__ arow,
+                                                         const double* (&xs)[NV], int64_t cb, int64_t lo,
+                                                         int64_t hi, bool fwd) {
+    dbl2x ta[W / 2], tx[NV][W / 2];
+#pragma unroll
+    for (int v = 0; v < W / 2; ++v) {
+        const int64_t j0 = cb + 2 * v, j1 = j0 + 1;
+        const bool in0 = j0 >= lo && j0 < hi, in1 = j1 >= lo && j1 < hi;
+        ta[v] = dbl2x{in0 ? arow[j0] : 0.0, in1 ? arow[j1] : 0.0};
+#pragma unroll
+        for (int n = 0; n < NV; ++n) tx[n][v] = dbl2x{in0 ? xs[n][j0] : 0.0, in1 ? xs[n][j1] : 0.0};
+    }
+    if (fwd)
+        hop_segment_multi<L, W, NV, true>(sum, ta, tx);
+    else
+        hop_segment_multi<L, W, NV, false>(sum, ta, tx);
+}
+
+// hop_chain for NV chains: U slots of a segment's A and of its NV x pieces; prime, groups and
+// drain as there. load(g, i, a, xv) loads segment g into slot i.
+template <int L, int W, int U, int NV, bool FWD0, class LOAD>
+__device__ __forceinline__ void hop_chain_multi(double (&sum)[NV], int64_t nseg, LOAD&& load) {
+    static_assert(U % 2 == 0, "slot i keeps the direction of its parity across groups");
+    constexpr int V = W / 2;
+    if (nseg <= 0) return;
+    dbl2x a[U][V], xv[U][NV][V];
+    auto step = [&](int i) {
+        if (i & 1)
+            hop_segment_multi<L, W, NV, !FWD0>(sum, a[i], xv[i]);
+        else
+            hop_segment_multi<L, W, NV, FWD0>(sum, a[i], xv[i]);
+    };
+#pragma unroll
+    for (int i = 0; i < U; ++i) {
+        load(i < nseg ? i : nseg - 1, i, a[i], xv[i]);
+        __builtin_amdgcn_sched_barrier(0);  // same load order as the loop's refills
+    }
+    int64_t base = 0;
+    for (; base + U < nseg; base += U) {
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            step(i);
+            __builtin_amdgcn_sched_barrier(0);
+            load(base + i + U < nseg ? base + i + U : nseg - 1, i, a[i], xv[i]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < U; ++i)
+        if (base + i < nseg) step(i);
+}
+
+// Head, main segments, tails and holder lane are the row's, as in gemv_seq_hop, and shared by
+// the NV chains. A by 8-B loads (any alignment, any lda), X by 8-B loads (any ldx). Vector n of
+// the group is X + n*ldx -> Y + n*ldy; with nvl < NV the chains past nvl repeat vector nvl - 1
+// and store nothing (the last group of a block whose size is not a multiple of NV).
+template <int L, int W, int U, int NV>
+__global__ __launch_bounds__(64) void gemv_seq_hop_multi(const double* __restrict__ A, int64_t lda,
+                                                         const double* __restrict__ X, int64_t ldx,
+                                                         double* __restrict__ Y, int64_t ldy, int64_t M, int64_t K,
+                                                         int nvl) {
+    static_assert(L == 8 || L == 16 || L == 32, "lanes per row");
+    static_assert(W % 2 == 0 && U % 2 == 0, "whole 16-B pieces; segment pairs per unrolled step");
+    static_assert(NV >= 2, "one vector: gemv_seq_hop");
+    constexpr int R = 64 / L;  // rows per wave
+    constexpr int S = L * W;   // columns per segment
+    constexpr int V = W / 2;   // 16-B pieces per lane per segment
+    static_assert(S >= 16, "the head (up to 15 columns) fits one segment");
+    const int lane = threadIdx.x & 63;
+    const int c = lane % L;
+    const int64_t row = (int64_t)blockIdx.x * R + lane / L;
+    const int64_t rr = row < M ? row : M - 1;
+    const double* arow = A + rr * lda;
+    const double* xs[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) xs[n] = X + (int64_t)(n < nvl ? n : nvl - 1) * ldx;
+    const int off[2] = {c * W, (L - 1 - c) * W};  // even / odd segment
+    double sum[NV];
+#pragma unroll
+    for (int n = 0; n < NV; ++n) sum[n] = 0.0;
+    int64_t nseg = 0, ntail = 0;
+    if (K > 0) {
+        const int64_t h = (int64_t)(((128u - ((uintptr_t)arow & 127u)) & 127u) >> 3);
+        hop_masked_segment_multi<L, W, NV>(sum, arow, xs, h - S + off[0], 0, h < K ? h : K, true);
+        nseg = lines_aligned(A, lda) ? K / S : K >= 15 ? (K - 15) / S : 0;
+        ntail = (K - nseg * S + S - 1) / S;  // 0, 1 or 2 tail segments, as in gemv_seq_hop
+        const double* ar = arow + h;
+        // main segment sg is the row's segment sg + 1 (after the head): slot 0 runs backwards
+        hop_chain_multi<L, W, U, NV, false>(sum, nseg, [&](int64_t sg, int i, dbl2x (&da)[V], dbl2x (&dx)[NV][V]) {
+            const int64_t col = sg * S + off[(i + 1) & 1];
+            load_run<V, true, true>(ar + col, da);
+#pragma unroll
+            for (int n = 0; n < NV; ++n) load_run<V, true, false>(xs[n] + h + col, dx[n]);
+        });
+        for (int64_t t = 0; t < ntail; ++t) {
+            const int64_t g = 1 + nseg + t;  // the row's segment index
+            hop_masked_segment_multi<L, W, NV>(sum, arow, xs, h + (nseg + t) * S + off[g & 1], h, K, (g & 1) == 0);
+        }
+    }
+    // the chains end in lane L-1 after an odd number of segments, in lane 0 otherwise
+    const int holder = (K > 0 && ((1 + nseg + ntail) & 1)) ? L - 1 : 0;
+    if (c == holder && row < M) {
+#pragma unroll
+        for (int n = 0; n < NV; ++n)
+            if (n < nvl) Y[n * ldy + row] = sum[n];
+    }
+}
+
 // ------------------------------------------------------------------ column-panel layout
 // Every exact form streams all M rows at once — a row's chain (>= 2.5 ns per column) is too slow
 // for the tree kernel's sliding window of a thousand rows — so at any moment it reads M scattered
@@ -850,6 +990,78 @@ constexpr int64_t kPanelWidth = 256;
 // inside the box-to-box spread, so round 3 dropped that threshold
 static int pick_panel_variant(int64_t) { return kPanelRows; }
 
+// ------------------------------------------------------------------ multi-vector variant table
+// gemv_seq_hop_multi<L, W, U, NV>: hopm_l<L>_w<W>_u<U>_v<NV>, NV chains per row over U slots of
+// (1 + NV) x W/2 16-B pieces each. The single-vector picks hold 128 operand VGPRs (hop8_l8_w2_u16:
+// 16 x 2 x 1 pieces); with NV vectors the same slot count would need (1 + NV)/2 times that, so
+// the forms here trade slots for chains. One-wave workgroups, no LDS, no scratch. Registers and
+// waves per SIMD as hipcc -Rpass-analysis=kernel-resource-usage reports them for gfx950
+// (512 VGPRs per lane per SIMD; accumulation registers unused):
+//   hopm_l8_w2_u8_v2   127 VGPRs  4 waves     hopm_l8_w2_u4_v4   126 VGPRs  4 waves
+//   hopm_l8_w2_u16_v2  223 VGPRs  2 waves     hopm_l8_w2_u8_v4   203 VGPRs  2 waves
+//   hopm_l16_w4_u4_v2  128 VGPRs  4 waves     hopm_l16_w4_u2_v4  125 VGPRs  4 waves
+//   hopm_l16_w4_u8_v2  221 VGPRs  2 waves     hopm_l16_w4_u4_v4  210 VGPRs  2 waves
+//   hopm_l32_w8_u2_v2  127 VGPRs  4 waves     hopm_l32_w8_u2_v4  209 VGPRs  2 waves
+//   hopm_l32_w8_u4_v2  222 VGPRs  2 waves     hopm_l32_w4_u4_v4  210 VGPRs  2 waves
+// every one with 0 bytes of scratch and no spilled register
+typedef void (*seq_multi_fn)(const double*, int64_t, const double*, int64_t, double*, int64_t, int64_t, int64_t, int);
+struct SeqMultiVariant {
+    const char* name;
+    seq_multi_fn fn;  // nullptr: one mvg_gemv_exact per vector
+    int nv;           // chains per pass
+    int rows;         // rows per one-wave workgroup
+};
+#define HOPM(L, W, U, NV) {"hopm_l" #L "_w" #W "_u" #U "_v" #NV, gemv_seq_hop_multi<L, W, U, NV>, NV, 64 / L}
+static constexpr SeqMultiVariant kSeqMultiVariants[] = {
+    {"auto", nullptr, 1, 8},      // 0
+    {"separate", nullptr, 1, 8},  // a pass of mvg_gemv_exact per vector: what auto takes where no form below won its sweep
+    HOPM(8, 2, 8, 2),
+    HOPM(8, 2, 16, 2),
+    HOPM(16, 4, 4, 2),
+    HOPM(16, 4, 8, 2),
+    HOPM(32, 8, 2, 2),
+    HOPM(32, 8, 4, 2),
+    HOPM(8, 2, 4, 4),
+    HOPM(8, 2, 8, 4),
+    HOPM(16, 4, 2, 4),
+    HOPM(16, 4, 4, 4),
+    HOPM(32, 8, 2, 4),
+    HOPM(32, 4, 4, 4),
+};
+#undef HOPM
+constexpr int kNumSeqMultiVariants = (int)(sizeof(kSeqMultiVariants) / sizeof(kSeqMultiVariants[0]));
+constexpr int kMultiSeparate = variant_id(kSeqMultiVariants, "separate");
+constexpr int kMultiRows2 = variant_id(kSeqMultiVariants, "hopm_l8_w2_u8_v2");
+constexpr int kMultiRows4 = variant_id(kSeqMultiVariants, "hopm_l8_w2_u4_v4");
+constexpr int kMultiWide2 = variant_id(kSeqMultiVariants, "hopm_l16_w4_u4_v2");
+constexpr int kMultiWide4 = variant_id(kSeqMultiVariants, "hopm_l16_w4_u4_v4");
+constexpr int kMultiFewRows2 = variant_id(kSeqMultiVariants, "hopm_l32_w8_u4_v2");
+static_assert(kMultiSeparate > 0 && kMultiRows2 > 0 && kMultiRows4 > 0 && kMultiWide2 > 0 && kMultiWide4 > 0 &&
+                  kMultiFewRows2 > 0,
+              "multi dispatch names a missing variant");
+
+// The variant for a group of g = 2 or 4 vectors. The house rule: a multi form only
+// for a (rows class, K class, group size) in which tools/exact_multi_sweep.py showed it more than
+// 2 % faster than that many mvg_gemv_exact calls (profiles/r07/exact_multi/sweep_all.jsonl, one
+// MI355X, medians of 7 interleaved rounds; ratio = separate passes' time / the multi pass's);
+// the classes are the single-vector dispatch's (pick_seq_variant), and every other class keeps
+// the separate passes, which define the result anyway:
+//   >= 6144 rows, K < 65536 (8 lanes; 16384^2, 65536 x 8192, 524288 x 512):
+//       2 vectors hopm_l8_w2_u8_v2 1.73-1.76, 4 vectors hopm_l8_w2_u4_v4 2.08-2.28
+//       (16384^2: 356 us for 2, 593 us for 4, against 310 us for one);
+//   2048 .. 6143 rows, K > 8192 outside the 64-B corner (16 lanes x 32 B; 4096 x 16384):
+//       2 vectors hopm_l16_w4_u4_v2 1.34-1.47, 4 vectors hopm_l16_w4_u4_v4 1.57-1.69;
+//   < 2048 rows, K > 4096 (32 lanes; 1024 x 32768): 2 vectors hopm_l32_w8_u4_v2 1.15-1.18; the
+//       4-chain forms reach only 1.07-1.10 there, so a group of 4 goes out as two passes of 2.
+// Not swept, so separate passes: K >= 65536 with >= 6144 rows, 2048 .. 6143 rows of K <= 8192 or
+// in the 64-B corner (< 4096 rows, K >= 32768), < 2048 rows of K <= 4096.
+static int pick_seq_multi_variant(int64_t, int64_t, int64_t M, int64_t K, int g) {
+    const bool four = g >= 4;
+    if (M >= 6144) return K >= 65536 ? kMultiSeparate : four ? kMultiRows4 : kMultiRows2;
+    if (M >= 2048) return K <= 8192 || (M < 4096 && K >= 32768) ? kMultiSeparate : four ? kMultiWide4 : kMultiWide2;
+    return K <= 4096 ? kMultiSeparate : kMultiFewRows2;
+}
+
 }  // namespace mvg
 
 using namespace mvg;
@@ -965,6 +1177,65 @@ int mvg_debug_combine_grid_rows(const double* parts, int gr, int gc, int64_t lr,
 int mvg_gemv_exact(const double* A, int64_t lda, const double* x, double* y, int64_t m, int64_t k,
                    void* stream) {
     return mvg_gemv_exact_variant(A, lda, x, y, m, k, 0, stream);
+}
+
+// ---- several vectors per pass (gemv_seq_hop_multi)
+int mvg_gemv_exact_multi_variant_count(void) { return kNumSeqMultiVariants; }
+
+const char* mvg_gemv_exact_multi_variant_name(int v) {
+    if (v < 0 || v >= kNumSeqMultiVariants) return "invalid";
+    return kSeqMultiVariants[v].name;
+}
+
+int mvg_gemv_exact_multi_auto_variant(int64_t lda, int64_t ldx, int64_t m, int64_t k, int nv) {
+    if (nv < 2) return 0;
+    return pick_seq_multi_variant(lda, ldx, m, k, nv >= 4 ? 4 : 2);  // the first group's
+}
+
+int mvg_gemv_exact_multi_variant(const double* A, int64_t lda, const double* X, int64_t ldx, double* Y, int64_t ldy,
+                                 int64_t m, int64_t k, int nv, int variant, void* stream) {
+    if (m < 0 || k < 0 || nv < 0) return fail(MVG_E_INVALID, "mvg_gemv_exact_multi: negative size");
+    if (variant < 0 || variant >= kNumSeqMultiVariants) return fail(MVG_E_INVALID, "mvg_gemv_exact_multi: bad variant");
+    if (m == 0 || nv == 0) return MVG_OK;
+    if (!Y || ldy < m || (k > 0 && (!A || !X || lda < k || ldx < k)))
+        return fail(MVG_E_INVALID, "mvg_gemv_exact_multi: null pointer or leading dimension too small");
+    if (int rc = take_pending_error("mvg_gemv_exact_multi"); rc != MVG_OK) return rc;
+    int v0 = 0;
+    // Groups of the variant's NV vectors. An explicit variant runs a last group of 2 .. NV - 1 on
+    // the same kernel with its spare chains idle; the automatic choice asks the dispatch again
+    // for what is left (groups of 4, then one of 2). A last single vector, and everything where
+    // the choice is "separate", goes to the single-vector dispatch below.
+    while (k > 0 && nv - v0 >= 2) {
+        const int v = variant == 0 ? pick_seq_multi_variant(lda, ldx, m, k, nv - v0 >= 4 ? 4 : 2) : variant;
+        const SeqMultiVariant& var = kSeqMultiVariants[v];
+        if (!var.fn) break;
+        // launches of fewer than 2^31 threads; short rows (K <= 768) in pieces of at most 1 GiB of
+        // A, as the single-vector launch loop (mvg_gemv_exact_variant)
+        int64_t max_rows = ((1ll << 31) / 64 - 1) * var.rows;
+        if (k <= kShortRowK) {
+            const int64_t cap = short_row_piece_rows(k, var.rows);
+            if (cap < max_rows) max_rows = cap;
+        }
+        const int g = nv - v0 < var.nv ? nv - v0 : var.nv;
+        for (int64_t r0 = 0; r0 < m; r0 += max_rows) {
+            const int64_t mm = m - r0 < max_rows ? m - r0 : max_rows;
+            hipLaunchKernelGGL(var.fn, dim3((unsigned)((mm + var.rows - 1) / var.rows)), dim3(64), 0, (hipStream_t)stream,
+                               A + r0 * lda, lda, X + v0 * ldx, ldx, Y + v0 * ldy + r0, ldy, mm, k, g);
+            MVG_HIP(hipGetLastError());
+        }
+        v0 += g;
+    }
+    // per vector (k == 0 included: every row's sum stays 0)
+    for (; v0 < nv; ++v0) {
+        const int rc = mvg_gemv_exact(A, lda, X ? X + v0 * ldx : X, Y + v0 * ldy, m, k, stream);
+        if (rc != MVG_OK) return rc;
+    }
+    return MVG_OK;
+}
+
+int mvg_gemv_exact_multi(const double* A, int64_t lda, const double* X, int64_t ldx, double* Y, int64_t ldy, int64_t m,
+                         int64_t k, int nv, void* stream) {
+    return mvg_gemv_exact_multi_variant(A, lda, X, ldx, Y, ldy, m, k, nv, 0, stream);
 }
 
 // ---- column-panel layout (gemv_seq_hop_panel; the engine's exact mode)

@@ -156,8 +156,10 @@ def gemv(d_A: int, lda: int, d_x: int, d_y: int, m: int, k: int, stream=None, va
         check(lib.mvg_gemv_variant(d_A, lda, d_x, d_y, m, k, variant, stream), "mvg_gemv")
 
 
-def multiply_multi(A: np.ndarray, X: np.ndarray) -> np.ndarray:
-    """Y = A X for a k x nv block of vectors in one pass over A (mvg_gemv_multi); returns m x nv."""
+def multiply_multi(A: np.ndarray, X: np.ndarray, exact: bool = False) -> np.ndarray:
+    """Y = A X for a k x nv block of vectors in one pass over A (mvg_gemv_multi); returns m x nv.
+    exact=True (mvg_gemv_exact_multi): every column bit-identical to the reference's
+    multiply_std_rowwise on that vector."""
     A = np.ascontiguousarray(A, dtype=np.float64)
     X = np.asarray(X, dtype=np.float64)
     R, Cn = A.shape
@@ -165,7 +167,10 @@ def multiply_multi(A: np.ndarray, X: np.ndarray) -> np.ndarray:
     Xc = np.ascontiguousarray(X.T)  # column-major: vector v contiguous
     dA, dX, dY = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(Cn * nv).upload(Xc), DeviceBuffer(R * nv)
     try:
-        check(lib.mvg_gemv_multi(dA.ptr, Cn, dX.ptr, Cn, dY.ptr, R, R, Cn, nv, None), "mvg_gemv_multi")
+        if exact:
+            check(lib.mvg_gemv_exact_multi(dA.ptr, Cn, dX.ptr, Cn, dY.ptr, R, R, Cn, nv, None), "mvg_gemv_exact_multi")
+        else:
+            check(lib.mvg_gemv_multi(dA.ptr, Cn, dX.ptr, Cn, dY.ptr, R, R, Cn, nv, None), "mvg_gemv_multi")
         check(lib.mvg_stream_sync(None), "sync")
         return dY.download(R * nv).reshape(nv, R).T.copy()
     finally:
@@ -338,6 +343,45 @@ class Multiplier:
         y = np.empty(max(self.R, 1), dtype=np.float64)
         check(lib.mvg_engine_collect(self.handle, y.ctypes.data), "mvg_engine_collect")
         return y[: self.R]
+
+    # ---- a block of vectors: Y = A X on the distributed A, one pass and one exchange per block
+    def set_vectors(self, X: np.ndarray | None, nv: int | None = None) -> None:
+        """Root's host X (C x nv, 1 <= nv <= 16) -> the whole X on every device. Off the root X
+        may be None; every rank then still names the same nv."""
+        if X is None:
+            if nv is None:
+                raise ValueError("set_vectors(None) needs nv")
+            self._keep_X = None
+            check(lib.mvg_engine_set_vectors(self.handle, None, self.C, int(nv)), "mvg_engine_set_vectors")
+            return
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] != self.C or (nv is not None and nv != X.shape[1]):
+            raise ValueError(f"X has shape {X.shape}, A has {self.C} columns" + (f", nv = {nv}" if nv is not None else ""))
+        Xc = np.ascontiguousarray(X.T)  # column-major: vector v contiguous
+        self._keep_X = Xc
+        check(lib.mvg_engine_set_vectors(self.handle, Xc.ctypes.data, self.C, X.shape[1]), "mvg_engine_set_vectors")
+
+    def fill_synth_vectors(self, seed_x: int = SEED_X, nv: int = 1) -> None:
+        check(lib.mvg_engine_fill_synth_vectors(self.handle, seed_x, int(nv)), "mvg_engine_fill_synth_vectors")
+
+    @property
+    def vectors(self) -> int:
+        n = C.c_int()
+        check(lib.mvg_engine_vectors(self.handle, C.byref(n)), "mvg_engine_vectors")
+        return n.value
+
+    def multiply_multi(self) -> None:
+        check(lib.mvg_engine_multiply_multi(self.handle), "mvg_engine_multiply_multi")
+
+    def collect_multi(self) -> np.ndarray | None:
+        """Y (R x nv) on the root (None elsewhere)."""
+        if not self.is_root():
+            check(lib.mvg_engine_sync(self.handle), "mvg_engine_sync")
+            return None
+        nv = self.vectors
+        Y = np.empty((max(nv, 1), max(self.R, 1)), dtype=np.float64)
+        check(lib.mvg_engine_collect_multi(self.handle, Y.ctypes.data, Y.shape[1]), "mvg_engine_collect_multi")
+        return Y[:nv, : self.R].T.copy()
 
     def set_exact(self, on: bool) -> None:
         check(lib.mvg_engine_set_exact(self.handle, int(bool(on))), "mvg_engine_set_exact")
