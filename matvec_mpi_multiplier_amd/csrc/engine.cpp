@@ -76,10 +76,24 @@ constexpr int kRing = 8;
 constexpr int64_t kStageElems = (256ll << 20) / (int64_t)sizeof(double);
 int64_t g_stage_elems = kStageElems;  // what the next mvg_engine_create reads
 
+// One set of a rank's exchange buffers, by MVG_X_BUF_*, for nv vectors: every buffer is
+// column-major, one vector per column. The local product (ld = y_len) in a ring when an exchange
+// follows: multiply n writes parts[n % ring] while earlier exchanges still read the others.
+struct XBufs {
+    double* parts[kRing] = {};   // MVG_X_BUF_PART
+    double* row = nullptr;       // block-split row leader: the reduced slice (ld = y_len)
+    double* y = nullptr;         // rank 0: the full y (ld = R)
+    double* gathered = nullptr;  // rank 0, exact mode: vector v's P partials in rank order at v * P * y_len
+    double*& at(int id, int b) {
+        return id == MVG_X_BUF_PART ? parts[b] : id == MVG_X_BUF_ROW ? row : id == MVG_X_BUF_Y ? y : gathered;
+    }
+};
+
 // One rank's streams, events, buffers and communicators. The handles are plain values and
-// free_shard is the one place that releases them: frees need the shard's device current, and
-// the trace (mvg_debug_trace_exchange) builds Shards whose pointers are stand-in addresses
-// that must never reach hipFree.
+// free_shard is the one place that releases them (a block's buffers also when the block grows,
+// make_vector_buffers): frees need the shard's device current, and the trace
+// (mvg_debug_trace_exchange) builds Shards whose pointers are stand-in addresses that must
+// never reach hipFree.
 struct Shard {
     mvg_shard plan{};
     int device = 0;
@@ -102,30 +116,22 @@ struct Shard {
     int64_t panelP = 0, pstride = 0;
     bool panels_fresh = false;
     int64_t uses = 0;  // multiplies since dA was last written
-    // local product: plan.y_len doubles; a ring of kRing buffers when an exchange follows:
-    // multiply n writes dy_parts[n % ring] while earlier exchanges still read the others
-    double* dy_parts[kRing] = {};
-    hipEvent_t gemv_done[kRing] = {};  // GEMV into dy_parts[b] finished
-    hipEvent_t x_done[kRing] = {};     // exchange reading dy_parts[b] finished
+    // the single vector's exchange buffers (gathered: mvg_engine_set_exact) and the ring's events,
+    // which both kinds of multiply share: one slot counter (mvg_engine::nx)
+    XBufs one;
+    hipEvent_t gemv_done[kRing] = {};  // product into slot b's partial finished
+    hipEvent_t x_done[kRing] = {};     // exchange reading slot b's partial finished
     // chunked distribution (mvg_engine_set_overlap): row chunk c of A landed (copy_stream); the
     // next multiply runs the GEMV of chunk c behind it, while later chunks are still copying
     std::vector<hipEvent_t> chunk_ev;
     std::vector<int64_t> chunk_row;   // chunk c = rows [chunk_row[c], chunk_row[c + 1])
     hipEvent_t copy_ready = nullptr;  // s.stream's work before the copies (the last GEMV reads dA)
     bool chunks_pending = false;
-    double* dy_row = nullptr;   // block-split row leader: reduced slice (lr doubles)
-    double* dy = nullptr;       // rank 0: the full y (R doubles)
-    double* gbuf = nullptr;     // rank 0, exact mode: every rank's partial, gathered in rank order
     // a block of vectors (mvg_engine_set_vectors): the whole X (C x nv, ld = C) on every rank, and
-    // exchange buffers of nv columns, their own so that the single vector's y and its ring stay
-    // what the last mvg_engine_multiply left: the ring of partials (ld = y_len), the grid-row
-    // buffer (ld = y_len), rank 0's Y (ld = R) and exact mode's gather buffer (vector v's P
-    // partials at v * P * y_len; made by the first exact mvg_engine_multiply_multi)
+    // exchange buffers of nv_cap columns, their own so that the single vector's y and its ring stay
+    // what the last mvg_engine_multiply left (gathered: the first exact mvg_engine_multiply_multi)
     double* dX = nullptr;
-    double* dY_parts[kRing] = {};
-    double* dY_row = nullptr;
-    double* dY = nullptr;
-    double* gbuf_multi = nullptr;
+    XBufs blk;
     // root, one process per GPU (root_send_shards): two staging buffers of stage_elems doubles in
     // one allocation, and the events that order their H2D copies and sends; made on first use
     double* stage = nullptr;
@@ -176,9 +182,8 @@ struct XOps {
     // op: MVG_X_GATHER or MVG_X_REDUCE (fp64 sum) of `count` doubles to `root`
     virtual ncclResult_t collective(int op, const double* src, double* dst, size_t count, int root, ncclComm_t comm,
                                     hipStream_t st) = 0;
-    virtual int combine(const mvg_engine* e, const Shard& s, hipStream_t st) = 0;
-    // the same combine for one vector of a block: rank 0's gathered partials of it -> its y
-    virtual int combine_vector(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t st) = 0;
+    // exact mode's combine of one vector: rank 0's gathered partials of it -> its y
+    virtual int combine(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t st) = 0;
 };
 
 struct DeviceXOps final : XOps {
@@ -193,12 +198,7 @@ struct DeviceXOps final : XOps {
         return op == MVG_X_GATHER ? ncclGather(src, dst, count, ncclFloat64, root, comm, st)
                                   : ncclReduce(src, dst, count, ncclFloat64, ncclSum, root, comm, st);
     }
-    int combine(const mvg_engine* e, const Shard& s, hipStream_t st) override {
-        return e->alg == MVG_ALG_COLWISE ? launch_combine_mpich_reduce(s.gbuf, e->nranks, e->R, s.dy, st)
-                                         : launch_combine_grid_rows(s.gbuf, s.plan.grid_rows, s.plan.grid_cols,
-                                                                    s.plan.y_len, s.dy, st);
-    }
-    int combine_vector(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t st) override {
+    int combine(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t st) override {
         return e->alg == MVG_ALG_COLWISE ? launch_combine_mpich_reduce(parts, e->nranks, e->R, y, st)
                                          : launch_combine_grid_rows(parts, s.plan.grid_rows, s.plan.grid_cols,
                                                                     s.plan.y_len, y, st);
@@ -304,33 +304,41 @@ int alloc_doubles(double** p, int64_t n) {
     return MVG_E_NOMEM;
 }
 
-// The block-of-vectors buffers of a shard (its device current, nothing in flight on them):
-// free_shard, and make_vector_buffers when the block grows.
-void release_vector_buffers(Shard& s) {
-    for (double** p : {&s.dX, &s.dY_row, &s.dY, &s.gbuf_multi}) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-    }
-    for (int b = 0; b < kRing; ++b) {
-        if (s.dY_parts[b]) (void)hipFree(s.dY_parts[b]);
-        s.dY_parts[b] = nullptr;
-    }
+// A shard's exchange buffers for nv vectors with a ring of `ring` partials (its device current),
+// all but exact mode's gather buffer, which alloc_gathered makes when the mode first needs it.
+int alloc_xbufs(const mvg_engine& e, const Shard& s, XBufs& x, int nv, int ring) {
+    const XBufLens xb = exchange_buffers(e, s, false);
+    for (int b = 0; b < ring; ++b) MVG_TRY(alloc_doubles(&x.parts[b], xb.len[MVG_X_BUF_PART] * nv));
+    MVG_TRY(alloc_doubles(&x.row, xb.len[MVG_X_BUF_ROW] * nv));
+    return alloc_doubles(&x.y, xb.len[MVG_X_BUF_Y] * nv);
+}
+int alloc_gathered(const mvg_engine& e, const Shard& s, XBufs& x, int nv, bool exact) {
+    if (x.gathered) return MVG_OK;
+    return alloc_doubles(&x.gathered, exchange_buffers(e, s, exact).len[MVG_X_BUF_GATHERED] * nv);
+}
+
+// The shard's device current, nothing in flight on the buffers: free_shard, and
+// make_vector_buffers when the block grows.
+void free_xbufs(XBufs& x) {
+    for (double* p : x.parts)
+        if (p) (void)hipFree(p);
+    for (double* p : {x.row, x.y, x.gathered})
+        if (p) (void)hipFree(p);
+    x = XBufs{};
 }
 
 void free_shard(Shard& s) {
     (void)hipSetDevice(s.device);
     for (hipStream_t st : {s.stream, s.copy_stream, s.xstream})
         if (st) (void)hipStreamSynchronize(st);
-    release_vector_buffers(s);
-    for (double* p : {s.dA, s.dAp, s.dx, s.dy_row, s.dy, s.stage, s.gbuf})
+    free_xbufs(s.one);
+    free_xbufs(s.blk);
+    for (double* p : {s.dA, s.dAp, s.dx, s.dX, s.stage})
         if (p) (void)hipFree(p);
     std::vector<hipEvent_t> events = {s.span_t0, s.span_t1, s.copy_ready, s.copied[0], s.copied[1],
                                       s.sent[0], s.sent[1],  s.ready};
     events.insert(events.end(), s.chunk_ev.begin(), s.chunk_ev.end());
-    for (int b = 0; b < kRing; ++b) {
-        if (s.dy_parts[b]) (void)hipFree(s.dy_parts[b]);
-        events.insert(events.end(), {s.gemv_done[b], s.x_done[b]});
-    }
+    for (int b = 0; b < kRing; ++b) events.insert(events.end(), {s.gemv_done[b], s.x_done[b]});
     for (auto& pair : s.ev_pool) events.insert(events.end(), {pair.first, pair.second});
     for (hipEvent_t ev : events)
         if (ev) (void)hipEventDestroy(ev);
@@ -456,6 +464,23 @@ int shard_pieces(const mvg_shard& p, int64_t stage, std::vector<Piece>* out) {
 
 hipEvent_t last_x_done(const mvg_engine* e, const Shard& s) { return s.x_done[(e->nx - 1) % e->ring]; }
 
+// Rank 0's shard, where this process holds it: the root's arguments are checked and y is
+// collected only there.
+Shard* root_shard(mvg_engine* e) {
+    for (auto& s : e->shards)
+        if (s.rank == 0) return &s;
+    return nullptr;
+}
+
+// The synthetic fills return with the data in place.
+int sync_gemv_streams(mvg_engine* e) {
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        MVG_HIP(hipStreamSynchronize(s.stream));
+    }
+    return MVG_OK;
+}
+
 // Rank 0 stages each peer's shard through two device buffers and ncclSend's it over xGMI (the
 // reference's sequential root Send loop, colwise.c:33-57), overlapping the next piece's H2D
 // with the current piece's send; then copies its own shard.
@@ -506,101 +531,65 @@ int recv_shard(const mvg_engine* e, Shard& s) {
     return MVG_OK;
 }
 
-// The exchange step from the shared schedule (mvg_plan_exchange): one group per step, every
-// local member issuing its call in it, out of ring slot b.
-int exchange_plan(mvg_engine* e, int b, bool serial, XOps& ops) {
+// ---- one multiply's exchange out of ring slot b of a buffer set (Shard::one: mvg_engine_multiply,
+// nv = 1; Shard::blk: mvg_engine_multiply_multi over a block of nv vectors), as the engine and the
+// trace both issue it. Every buffer is column-major, one vector per column.
+// The steps of the shared schedule (mvg_plan_exchange): one group per step, every local member
+// issuing its calls in it. A reduce step moves the nv columns as one contiguous run of count * nv
+// doubles; a gather step moves vector v with its own call, into column v of the root's Y (ld = R:
+// the members' pieces of one vector make up a whole y), so Y needs no transposing pass.
+int exchange_plan(mvg_engine* e, XBufs Shard::*set, int b, int nv, bool serial, XOps& ops) {
     for (int k = 0; k < e->shards[0].nsteps; ++k) {
         const char* what = e->shards[0].steps[k].op == MVG_X_GATHER ? "ncclGather" : "ncclReduce";
         MVG_TRY(grouped(e->shards, ops, what, [&](Shard& s) {
             const mvg_xstep& st = s.steps[k];
             if (!st.member) return ncclSuccess;
             ops.set_device(s.device);
-            double* bufs[3] = {s.dy_parts[b], s.dy_row, s.dy};  // by MVG_X_BUF_*
-            double* dst = bufs[st.dst] ? bufs[st.dst] : s.dy_parts[b];  // recvbuff is only written on the root
-            return ops.collective(st.op, bufs[st.src], dst, (size_t)st.count, st.root, s.xcomm[k],
-                                  serial ? s.stream : s.xstream);
-        }));
-    }
-    return MVG_OK;
-}
-
-// Exact mode (mvg_engine_set_exact): every partial gathered to rank 0 in rank order, then added
-// there in the reference's order.
-int exchange_exact(mvg_engine* e, int b, bool serial, XOps& ops) {
-    MVG_TRY(grouped(e->shards, ops, "ncclGather (exact)", [&](Shard& s) {
-        ops.set_device(s.device);
-        // recvbuff is only written on the root
-        return ops.collective(MVG_X_GATHER, s.dy_parts[b], s.rank == 0 ? s.gbuf : s.dy_parts[b], (size_t)s.plan.y_len, 0,
-                              s.world, serial ? s.stream : s.xstream);
-    }));
-    for (auto& s : e->shards) {
-        if (s.rank != 0) continue;
-        ops.set_device(s.device);
-        MVG_TRY(ops.combine(e, s, serial ? s.stream : s.xstream));
-    }
-    return MVG_OK;
-}
-
-// One multiply's exchange out of ring slot b, as the engine and the trace both issue it.
-int exchange(mvg_engine* e, int b, bool serial, XOps& ops) {
-    return e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact(e, b, serial, ops) : exchange_plan(e, b, serial, ops);
-}
-
-// ---- the same exchange for a block of nv vectors (mvg_engine_multiply_multi), out of slot b of
-// the block's ring. Every buffer is column-major, one vector per column: a reduce step moves the
-// nv columns as one contiguous run of count * nv doubles; a gather step moves vector v with its
-// own call inside the step's one group, into column v of the root's Y (ld = R: the members'
-// pieces of one vector make up a whole y), so Y needs no transposing pass.
-int exchange_plan_multi(mvg_engine* e, int b, bool serial, int nv, XOps& ops) {
-    for (int k = 0; k < e->shards[0].nsteps; ++k) {
-        const char* what = e->shards[0].steps[k].op == MVG_X_GATHER ? "ncclGather" : "ncclReduce";
-        MVG_TRY(grouped(e->shards, ops, what, [&](Shard& s) {
-            const mvg_xstep& st = s.steps[k];
-            if (!st.member) return ncclSuccess;
-            ops.set_device(s.device);
-            double* bufs[3] = {s.dY_parts[b], s.dY_row, s.dY};  // by MVG_X_BUF_*
-            const bool writes = bufs[st.dst] != nullptr;  // recvbuff is only written on the root
-            double* dst = writes ? bufs[st.dst] : s.dY_parts[b];
+            XBufs& x = s.*set;
+            const double* src = x.at(st.src, b);
+            const bool writes = x.at(st.dst, b) != nullptr;  // recvbuff is only written on the root
+            double* dst = writes ? x.at(st.dst, b) : x.parts[b];
             hipStream_t stream = serial ? s.stream : s.xstream;
             if (st.op == MVG_X_REDUCE)
-                return ops.collective(st.op, bufs[st.src], dst, (size_t)st.count * nv, st.root, s.xcomm[k], stream);
+                return ops.collective(st.op, src, dst, (size_t)st.count * nv, st.root, s.xcomm[k], stream);
             ncclResult_t r = ncclSuccess;
             for (int v = 0; v < nv && r == ncclSuccess; ++v)
-                r = ops.collective(st.op, bufs[st.src] + v * st.count, writes ? dst + v * e->R : dst, (size_t)st.count,
-                                   st.root, s.xcomm[k], stream);
+                r = ops.collective(st.op, src + v * st.count, writes ? dst + v * e->R : dst, (size_t)st.count, st.root,
+                                   s.xcomm[k], stream);
             return r;
         }));
     }
     return MVG_OK;
 }
 
-// Exact mode: per vector the rank-order gather of exchange_exact (all nv in one group), then the
-// reference's combine once per vector, each as if that vector were alone (the MPICH algorithm
-// switch looks at one y's length).
-int exchange_exact_multi(mvg_engine* e, int b, bool serial, int nv, XOps& ops) {
+// Exact mode (mvg_engine_set_exact): per vector every partial gathered to rank 0 in rank order
+// (all nv in one group), then added there in the reference's order, once per vector, each as if
+// that vector were alone (the MPICH algorithm switch looks at one y's length).
+int exchange_exact(mvg_engine* e, XBufs Shard::*set, int b, int nv, bool serial, XOps& ops) {
     MVG_TRY(grouped(e->shards, ops, "ncclGather (exact)", [&](Shard& s) {
         ops.set_device(s.device);
+        XBufs& x = s.*set;
         const int64_t n = s.plan.y_len;
         ncclResult_t r = ncclSuccess;
-        for (int v = 0; v < nv && r == ncclSuccess; ++v)
-            r = ops.collective(MVG_X_GATHER, s.dY_parts[b] + v * n,
-                               s.rank == 0 ? s.gbuf_multi + v * e->nranks * n : s.dY_parts[b], (size_t)n, 0, s.world,
-                               serial ? s.stream : s.xstream);
+        for (int v = 0; v < nv && r == ncclSuccess; ++v)  // recvbuff is only written on the root
+            r = ops.collective(MVG_X_GATHER, x.parts[b] + v * n, s.rank == 0 ? x.gathered + v * e->nranks * n : x.parts[b],
+                               (size_t)n, 0, s.world, serial ? s.stream : s.xstream);
         return r;
     }));
     for (auto& s : e->shards) {
         if (s.rank != 0) continue;
         ops.set_device(s.device);
+        XBufs& x = s.*set;
         for (int v = 0; v < nv; ++v)
-            MVG_TRY(ops.combine_vector(e, s, s.gbuf_multi + v * e->nranks * s.plan.y_len, s.dY + v * e->R,
-                                       serial ? s.stream : s.xstream));
+            MVG_TRY(ops.combine(e, s, x.gathered + v * e->nranks * s.plan.y_len, x.y + v * e->R,
+                                serial ? s.stream : s.xstream));
     }
     return MVG_OK;
 }
 
-int exchange_multi(mvg_engine* e, int b, bool serial, int nv, XOps& ops) {
-    return e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact_multi(e, b, serial, nv, ops)
-                                                 : exchange_plan_multi(e, b, serial, nv, ops);
+int exchange(mvg_engine* e, XBufs Shard::*set, int b, int nv, bool serial, XOps& ops) {
+    return e->exact && e->alg != MVG_ALG_ROWWISE ? exchange_exact(e, set, b, nv, serial, ops)
+                                                 : exchange_plan(e, set, b, nv, serial, ops);
 }
 
 // The recorder behind mvg_debug_trace_exchange. Communicators and buffers are stand-in handles
@@ -663,15 +652,7 @@ struct TraceXOps final : XOps {
         calls.push_back(c);
         return ncclSuccess;
     }
-    int combine(const mvg_engine* e, const Shard& s, hipStream_t) override {
-        mvg_xcall c = base(MVG_XCALL_COMBINE);
-        c.count = s.plan.y_len * e->nranks;
-        c.src = buf_of(s.gbuf);
-        c.dst = buf_of(s.dy);
-        calls.push_back(c);
-        return MVG_OK;
-    }
-    int combine_vector(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t) override {
+    int combine(const mvg_engine* e, const Shard& s, double* parts, double* y, hipStream_t) override {
         mvg_xcall c = base(MVG_XCALL_COMBINE);
         c.count = s.plan.y_len * e->nranks;
         c.src = buf_of(parts);
@@ -695,8 +676,7 @@ int init_shard(mvg_engine* e, Shard& s, const LocalRank& l) {
     MVG_TRY(alloc_doubles(&s.dx, s.plan.n_cols));
     MVG_TRY(mvg_plan_exchange(e->alg, e->R, e->C, e->nranks, l.rank, e->always_collect, s.steps, MVG_MAX_XSTEPS,
                               &s.nsteps));
-    const XBufLens xb = exchange_buffers(*e, s, false);  // exact mode's buffer: mvg_engine_set_exact
-    for (int b = 0; b < (s.nsteps > 0 ? e->ring : 1); ++b) MVG_TRY(alloc_doubles(&s.dy_parts[b], xb.len[MVG_X_BUF_PART]));
+    MVG_TRY(alloc_xbufs(*e, s, s.one, 1, s.nsteps > 0 ? e->ring : 1));
     if (s.nsteps > 0) {
         MVG_HIP(hipStreamCreateWithFlags(&s.xstream, hipStreamNonBlocking));
         for (int b = 0; b < e->ring; ++b) {
@@ -707,8 +687,7 @@ int init_shard(mvg_engine* e, Shard& s, const LocalRank& l) {
             MVG_TRY(ensure_event(&s.x_done[b]));
         }
     }
-    MVG_TRY(alloc_doubles(&s.dy_row, xb.len[MVG_X_BUF_ROW]));
-    return alloc_doubles(&s.dy, xb.len[MVG_X_BUF_Y]);
+    return MVG_OK;
 }
 
 // Warm the device before any timed loop: first-touch every buffer (the first H2D into
@@ -724,10 +703,10 @@ int warm_shard(mvg_engine* e, Shard& s) {
     };
     MVG_TRY(zero(s.dA, p.n_rows * p.n_cols));
     MVG_TRY(zero(s.dx, p.n_cols));
-    for (int b = 0; b < kRing; ++b) MVG_TRY(zero(s.dy_parts[b], p.y_len));
-    MVG_TRY(zero(s.dy_row, p.y_len));
-    MVG_TRY(zero(s.dy, e->R));
-    MVG_TRY(mvg_gemv(s.dA, p.n_cols, s.dx, s.dy_parts[0], p.n_rows, p.n_cols, s.stream));
+    for (double* part : s.one.parts) MVG_TRY(zero(part, p.y_len));
+    MVG_TRY(zero(s.one.row, p.y_len));
+    MVG_TRY(zero(s.one.y, e->R));
+    MVG_TRY(mvg_gemv(s.dA, p.n_cols, s.dx, s.one.parts[0], p.n_rows, p.n_cols, s.stream));
     // ... and one page-locked H2D into A's buffer and D2H out of y's, as large as those
     // transfers will be up to 4 MiB, on each stream that distributes or collects. The
     // runtime brings its large-copy path up on the first such transfer of the process:
@@ -746,7 +725,7 @@ int warm_shard(mvg_engine* e, Shard& s) {
         if (we == hipSuccess && a_elems > 0)
             we = hipMemcpyAsync(s.dA, pinned, (size_t)a_elems * sizeof(double), hipMemcpyHostToDevice, st);
         if (we == hipSuccess && y_elems > 0)
-            we = hipMemcpyAsync(pinned, s.dy_parts[0], (size_t)y_elems * sizeof(double), hipMemcpyDeviceToHost, st);
+            we = hipMemcpyAsync(pinned, s.one.parts[0], (size_t)y_elems * sizeof(double), hipMemcpyDeviceToHost, st);
         if (we == hipSuccess) we = hipStreamSynchronize(st);
     }
     (void)hipHostFree(pinned);
@@ -862,6 +841,55 @@ int pool_collect(mvg_engine* e) {
         ++e->kernel_launches;
     }
     for (auto& s : e->shards) s.ev_used = 0;
+    return MVG_OK;
+}
+
+// ---- the frame of both multiplies: product(s, out) queues the shard's product into
+// `out` on s.stream; the exchange out of buffer set `set` follows on the exchange stream,
+// overlapping the next multiply's product. Both kinds share the slot counter and the events, so the
+// once-per-ring wait, x_pending and the collects' waits cover them in any mix.
+template <class Product>
+int multiply_step(mvg_engine* e, XBufs Shard::*set, int nv, Product product) {
+    const bool solo = e->shards[0].nsteps == 0;  // P == 1: the product goes straight into y
+    const bool serial = e->ring == 1;
+    const int b = solo ? 0 : (int)(e->nx % e->ring);
+    // The product writes parts[b]; the exchange that last read it was multiply nx - ring's. The
+    // GEMV stream waits once per ring, on the latest exchange (nx - 1): every slot is then free
+    // for the next `ring` GEMVs (the exchange stream runs in order), so one cross-stream wait is
+    // paid per ring instead of per multiply (measured: a wait per multiply cost more than the
+    // overlap saved at world size 1).
+    const bool wait_ring = !solo && !serial && e->x_pending && b == 0;
+    // 1) local product on every device
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        if (wait_ring) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+        MVG_TRY(product(s, solo ? (s.*set).y : (s.*set).parts[b]));
+        if (!solo && !serial) {  // hand over to the exchange stream
+            MVG_HIP(hipEventRecord(s.gemv_done[b], s.stream));
+            MVG_HIP(hipStreamWaitEvent(s.xstream, s.gemv_done[b], 0));
+        }
+    }
+    if (solo) return MVG_OK;
+    // 2) the exchange step
+    MVG_TRY(exchange(e, set, b, nv, serial, g_device_ops));
+    for (auto& s : e->shards) {
+        MVG_HIP(hipSetDevice(s.device));
+        if (!serial) MVG_HIP(hipEventRecord(s.x_done[b], s.xstream));
+    }
+    e->x_pending = !serial;
+    ++e->nx;
+    return MVG_OK;
+}
+
+// Both collects on rank 0's shard: y is complete once the last exchange is; copy(s) queues the
+// device-to-host copy on s.stream.
+template <class Copy>
+int collect_from(mvg_engine* e, Shard& s, Copy copy) {
+    DeviceGuard g;
+    MVG_HIP(hipSetDevice(s.device));
+    if (e->x_pending) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+    if (e->R > 0) MVG_TRY(copy(s));
+    MVG_HIP(hipStreamSynchronize(s.stream));
     return MVG_OK;
 }
 
@@ -1024,7 +1052,7 @@ int mvg_engine_set_exact(mvg_engine* e, int on) {
     // whatever can fail comes first: an error leaves the mode and the panel fields as they were
     for (auto& s : e->shards) {
         MVG_HIP(hipSetDevice(s.device));
-        if (!s.gbuf) MVG_TRY(alloc_doubles(&s.gbuf, exchange_buffers(*e, s, exact).len[MVG_X_BUF_GATHERED]));
+        MVG_TRY(alloc_gathered(*e, s, s.one, 1, exact));
     }
     e->exact = exact;
     for (auto& s : e->shards) {
@@ -1089,10 +1117,7 @@ int mvg_engine_fill_synth(mvg_engine* e, uint64_t seed_a, uint64_t seed_x) {
         MVG_TRY(mvg_synth_fill_device(s.dA, p.n_cols, p.n_rows, p.n_cols, p.row_off, p.col_off, e->C, seed_a, s.stream));
         MVG_TRY(mvg_synth_fill_device(s.dx, p.n_cols, 1, p.n_cols, 0, p.col_off, e->C, seed_x, s.stream));
     }
-    for (auto& s : e->shards) {
-        MVG_HIP(hipSetDevice(s.device));
-        MVG_HIP(hipStreamSynchronize(s.stream));
-    }
+    MVG_TRY(sync_gemv_streams(e));
     e->distributed = true;
     return MVG_OK;
 }
@@ -1102,8 +1127,7 @@ int mvg_engine_fill_synth(mvg_engine* e, uint64_t seed_a, uint64_t seed_x) {
 // One process per GPU: rank 0 sends every peer its shard (root_send_shards / recv_shard).
 int mvg_engine_distribute(mvg_engine* e, const double* A, const double* x) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
-    bool root = false;
-    for (auto& s : e->shards) root |= s.rank == 0;
+    const bool root = root_shard(e) != nullptr;
     if (root && (!x || (!A && e->R * e->C > 0))) return fail(MVG_E_INVALID, "root needs A and x");
     if (e->single_process) return distribute_direct(e, A, x);
     begin_write(e);
@@ -1142,45 +1166,20 @@ int mvg_engine_multiply(mvg_engine* e) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
     if (!e->distributed) return fail(MVG_E_STATE, "mvg_engine_multiply before distribute/fill");
     DeviceGuard g;
-    const bool solo = e->shards[0].nsteps == 0;  // P == 1: the product goes straight into y
-    const bool serial = e->ring == 1;
     bool chunked = false;  // a chunked distribution is pending: the GEMVs wait on copies, not timed
     for (auto& s : e->shards) chunked |= s.chunks_pending;
     const bool timed = pool_enter(e, chunked);
     const bool span_opens = span_enter(e, chunked);
-    const int b = solo ? 0 : (int)(e->nx % e->ring);
-    // The GEMV writes dy_parts[b]; the exchange that last read it was multiply nx - ring's. The
-    // GEMV stream waits once per ring, on the latest exchange (nx - 1): every slot is then free
-    // for the next `ring` GEMVs (the exchange stream runs in order), so one cross-stream wait is
-    // paid per ring instead of per multiply (measured: a wait per multiply cost more than the
-    // overlap saved at world size 1).
-    const bool wait_ring = !solo && !serial && e->x_pending && b == 0;
-    // 1) local product on every device
-    for (auto& s : e->shards) {
-        MVG_HIP(hipSetDevice(s.device));
-        if (wait_ring) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+    return multiply_step(e, &Shard::one, 1, [&](Shard& s, double* out) -> int {
         MVG_TRY(refresh_panels(e, s, span_opens));
         ++s.uses;
         hipEvent_t stop = nullptr;
         if (span_opens) MVG_TRY(span_start(s));
         if (timed) MVG_TRY(pool_start(s, &stop));
-        MVG_TRY(local_product(e, s, solo ? s.dy : s.dy_parts[b]));
+        MVG_TRY(local_product(e, s, out));
         if (stop) MVG_HIP(hipEventRecord(stop, s.stream));
-        if (!solo && !serial) {  // hand over to the exchange stream
-            MVG_HIP(hipEventRecord(s.gemv_done[b], s.stream));
-            MVG_HIP(hipStreamWaitEvent(s.xstream, s.gemv_done[b], 0));
-        }
-    }
-    if (solo) return MVG_OK;
-    // 2) the exchange step on the exchange stream, overlapping the next multiply's GEMV
-    MVG_TRY(exchange(e, b, serial, g_device_ops));
-    for (auto& s : e->shards) {
-        MVG_HIP(hipSetDevice(s.device));
-        if (!serial) MVG_HIP(hipEventRecord(s.x_done[b], s.xstream));
-    }
-    e->x_pending = !serial;
-    ++e->nx;
-    return MVG_OK;
+        return MVG_OK;
+    });
 }
 
 int mvg_engine_sync(mvg_engine* e) {
@@ -1209,18 +1208,13 @@ int mvg_engine_kernel_ms(mvg_engine* e, double* avg_ms, int64_t* launches) {
 
 int mvg_engine_collect(mvg_engine* e, double* y) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
-    DeviceGuard g;
-    for (auto& s : e->shards) {
-        if (s.rank != 0) continue;
-        if (!y) return fail(MVG_E_INVALID, "root needs a y buffer");
-        MVG_HIP(hipSetDevice(s.device));
-        if (e->x_pending)  // y is complete once the last exchange is
-            MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
-        if (e->R > 0)
-            MVG_HIP(hipMemcpyAsync(y, s.dy, (size_t)e->R * sizeof(double), hipMemcpyDeviceToHost, s.stream));
-        MVG_HIP(hipStreamSynchronize(s.stream));
-    }
-    return MVG_OK;
+    Shard* root = root_shard(e);
+    if (!root) return MVG_OK;
+    if (!y) return fail(MVG_E_INVALID, "root needs a y buffer");
+    return collect_from(e, *root, [&](Shard& s) -> int {
+        MVG_HIP(hipMemcpyAsync(y, s.one.y, (size_t)e->R * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+        return MVG_OK;
+    });
 }
 
 // ------------------------------------------------------------------ a block of vectors
@@ -1239,13 +1233,11 @@ int make_vector_buffers(mvg_engine* e, int nv) {
         MVG_HIP(hipSetDevice(s.device));
         MVG_HIP(hipStreamSynchronize(s.stream));
         if (s.xstream) MVG_HIP(hipStreamSynchronize(s.xstream));
-        release_vector_buffers(s);
-        const XBufLens xb = exchange_buffers(*e, s, false);
+        free_xbufs(s.blk);
+        if (s.dX) (void)hipFree(s.dX);
         MVG_TRY(alloc_doubles(&s.dX, e->C * nv));
-        if (s.nsteps > 0)  // alone (no exchange) the product goes straight into Y
-            for (int b = 0; b < e->ring; ++b) MVG_TRY(alloc_doubles(&s.dY_parts[b], xb.len[MVG_X_BUF_PART] * nv));
-        MVG_TRY(alloc_doubles(&s.dY_row, xb.len[MVG_X_BUF_ROW] * nv));
-        MVG_TRY(alloc_doubles(&s.dY, xb.len[MVG_X_BUF_Y] * nv));
+        // alone (no exchange) the product goes straight into Y: no ring
+        MVG_TRY(alloc_xbufs(*e, s, s.blk, nv, s.nsteps > 0 ? e->ring : 0));
     }
     e->nv_cap = nv;
     return MVG_OK;
@@ -1264,8 +1256,7 @@ int begin_vectors(mvg_engine* e, int nv, const char* who) {
 
 int mvg_engine_set_vectors(mvg_engine* e, const double* X, int64_t ldx, int nv) {
     MVG_TRY(begin_vectors(e, nv, "mvg_engine_set_vectors"));
-    bool root = false;
-    for (auto& s : e->shards) root |= s.rank == 0;
+    const bool root = root_shard(e) != nullptr;
     if (root && e->C > 0 && (!X || ldx < e->C)) return fail(MVG_E_INVALID, "mvg_engine_set_vectors: root needs X with ldx >= C");
     DeviceGuard g;
     MVG_TRY(make_vector_buffers(e, nv));
@@ -1293,10 +1284,7 @@ int mvg_engine_fill_synth_vectors(mvg_engine* e, uint64_t seed_x, int nv) {
         MVG_HIP(hipSetDevice(s.device));
         MVG_TRY(mvg_synth_fill_device(s.dX, e->C, nv, e->C, 0, 0, e->C, seed_x, s.stream));
     }
-    for (auto& s : e->shards) {
-        MVG_HIP(hipSetDevice(s.device));
-        MVG_HIP(hipStreamSynchronize(s.stream));
-    }
+    MVG_TRY(sync_gemv_streams(e));
     e->nv = nv;
     return MVG_OK;
 }
@@ -1318,53 +1306,27 @@ int mvg_engine_multiply_multi(mvg_engine* e) {
     DeviceGuard g;
     if (span_is_open(e)) e->span_valid = false;  // not a GEMV of the span
     const int nv = e->nv;
-    const bool solo = e->shards[0].nsteps == 0;
-    const bool serial = e->ring == 1;
-    const int b = solo ? 0 : (int)(e->nx % e->ring);
-    const bool wait_ring = !solo && !serial && e->x_pending && b == 0;
-    for (auto& s : e->shards) {
-        MVG_HIP(hipSetDevice(s.device));
-        if (wait_ring) MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
+    return multiply_step(e, &Shard::blk, nv, [&](Shard& s, double* out) -> int {
         MVG_TRY(drain_chunks(s));  // a chunked distribution still copying: wait, then multiply whole
+        if (e->exact) MVG_TRY(alloc_gathered(*e, s, s.blk, e->nv_cap, true));
         const mvg_shard& p = s.plan;
-        if (e->exact && !solo && e->alg != MVG_ALG_ROWWISE && s.rank == 0 && !s.gbuf_multi)
-            MVG_TRY(alloc_doubles(&s.gbuf_multi, exchange_buffers(*e, s, true).len[MVG_X_BUF_GATHERED] * e->nv_cap));
         const double* X = s.dX ? s.dX + p.col_off : nullptr;
-        double* out = solo ? s.dY : s.dY_parts[b];
-        MVG_TRY(e->exact ? mvg_gemv_exact_multi(s.dA, p.n_cols, X, e->C, out, p.y_len, p.n_rows, p.n_cols, nv, s.stream)
-                         : mvg_gemv_multi(s.dA, p.n_cols, X, e->C, out, p.y_len, p.n_rows, p.n_cols, nv, s.stream));
-        if (!solo && !serial) {
-            MVG_HIP(hipEventRecord(s.gemv_done[b], s.stream));
-            MVG_HIP(hipStreamWaitEvent(s.xstream, s.gemv_done[b], 0));
-        }
-    }
-    if (solo) return MVG_OK;
-    MVG_TRY(exchange_multi(e, b, serial, nv, g_device_ops));
-    for (auto& s : e->shards) {
-        MVG_HIP(hipSetDevice(s.device));
-        if (!serial) MVG_HIP(hipEventRecord(s.x_done[b], s.xstream));
-    }
-    e->x_pending = !serial;
-    ++e->nx;
-    return MVG_OK;
+        return e->exact ? mvg_gemv_exact_multi(s.dA, p.n_cols, X, e->C, out, p.y_len, p.n_rows, p.n_cols, nv, s.stream)
+                        : mvg_gemv_multi(s.dA, p.n_cols, X, e->C, out, p.y_len, p.n_rows, p.n_cols, nv, s.stream);
+    });
 }
 
 int mvg_engine_collect_multi(mvg_engine* e, double* Y, int64_t ldy) {
     if (!e) return fail(MVG_E_INVALID, "null engine");
     if (e->nv == 0) return fail(MVG_E_STATE, "mvg_engine_collect_multi before set_vectors/fill_synth_vectors");
-    DeviceGuard g;
-    for (auto& s : e->shards) {
-        if (s.rank != 0) continue;
-        if (!Y || ldy < e->R) return fail(MVG_E_INVALID, "root needs a Y buffer with ldy >= R");
-        MVG_HIP(hipSetDevice(s.device));
-        if (e->x_pending)  // Y is complete once the last exchange is
-            MVG_HIP(hipStreamWaitEvent(s.stream, last_x_done(e, s), 0));
-        if (e->R > 0)
-            MVG_HIP(hipMemcpy2DAsync(Y, (size_t)ldy * sizeof(double), s.dY, (size_t)e->R * sizeof(double),
-                                     (size_t)e->R * sizeof(double), (size_t)e->nv, hipMemcpyDeviceToHost, s.stream));
-        MVG_HIP(hipStreamSynchronize(s.stream));
-    }
-    return MVG_OK;
+    Shard* root = root_shard(e);
+    if (!root) return MVG_OK;
+    if (!Y || ldy < e->R) return fail(MVG_E_INVALID, "root needs a Y buffer with ldy >= R");
+    return collect_from(e, *root, [&](Shard& s) -> int {
+        MVG_HIP(hipMemcpy2DAsync(Y, (size_t)ldy * sizeof(double), s.blk.y, (size_t)e->R * sizeof(double),
+                                 (size_t)e->R * sizeof(double), (size_t)e->nv, hipMemcpyDeviceToHost, s.stream));
+        return MVG_OK;
+    });
 }
 
 // Test hooks of the root-send staging (no device needed). The staging size that engines created
@@ -1399,7 +1361,8 @@ int mvg_debug_shard_pieces(int alg, int64_t R, int64_t C, int nranks, int rank, 
 // the shards the engine would create over G local devices (the same planner, the same buffer
 // choices), their communicator splits and one multiply's exchange, issued through the recorder
 // instead of RCCL (exchange_buffers, split_steps, exchange: the engine's own code).
-// nv = 0: one multiply's exchange; nv >= 1: one multiply_multi's over a block of nv vectors.
+// nv = 0: one multiply's exchange out of the single vector's buffer set; nv >= 1: one
+// multiply_multi's out of the block's. The stand-in addresses go into that set through XBufs::at.
 static int trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, int nv, mvg_xcall* calls, int max_calls,
                           int* ncalls) {
     if (!calls || !ncalls || ndev <= 0 || max_calls < 0 || nv < 0 || nv > MVG_MAX_VECTORS)
@@ -1414,6 +1377,7 @@ static int trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, in
     e.exact = exact != 0;
     e.shards.resize(ndev);
     TraceXOps ops;
+    XBufs Shard::*set = nv > 0 ? &Shard::blk : &Shard::one;
     auto fake = [&](int r, int id) {
         const uintptr_t a = ((uintptr_t)(r + 1) << 44) + (uintptr_t)(id + 1) * TraceXOps::kBufSpan;
         ops.buffers.push_back({a, {r, id}});
@@ -1428,14 +1392,11 @@ static int trace_exchange(int alg, int64_t R, int64_t C, int ndev, int exact, in
         MVG_TRY(mvg_plan_shard(alg, R, C, ndev, r, &s.plan));
         MVG_TRY(mvg_plan_exchange(alg, R, C, ndev, r, 0, s.steps, MVG_MAX_XSTEPS, &s.nsteps));
         const XBufLens xb = exchange_buffers(e, s, e.exact);
-        double** single[4] = {&s.dy_parts[0], &s.dy_row, &s.dy, &s.gbuf};  // by MVG_X_BUF_*
-        double** block[4] = {&s.dY_parts[0], &s.dY_row, &s.dY, &s.gbuf_multi};
-        double*** slot = nv > 0 ? block : single;
         for (int id = 0; id < 4; ++id)
-            if (xb.len[id] >= 0) *slot[id] = fake(r, id);
+            if (xb.len[id] >= 0) (s.*set).at(id, 0) = fake(r, id);
     }
     MVG_TRY(split_steps(e.shards, ops));
-    if (e.shards[0].nsteps > 0) MVG_TRY(nv > 0 ? exchange_multi(&e, 0, false, nv, ops) : exchange(&e, 0, false, ops));
+    if (e.shards[0].nsteps > 0) MVG_TRY(exchange(&e, set, 0, std::max(nv, 1), false, ops));
     if ((int)ops.calls.size() > max_calls) return fail(MVG_E_INVALID, "mvg_debug_trace_exchange: calls buffer too small");
     for (size_t i = 0; i < ops.calls.size(); ++i) calls[i] = ops.calls[i];
     *ncalls = (int)ops.calls.size();

@@ -191,6 +191,42 @@ def test_exchange_trace_matches_the_recorded_fixture():
         assert len(splits) == 2 * G
 
 
+def test_exchange_trace_of_a_block_matches_the_recorded_fixture():
+    """The same for one multiply_multi's exchange over a block of nv = 3 vectors
+    (mvg_debug_trace_exchange_multi) against tests/golden/exchange_traces_multi.json: a reduce step
+    as one call of count * nv, a gather step as nv calls, exact mode as nv gathers and nv combines."""
+    with open(os.path.join(GOLDEN_DIR, "exchange_traces_multi.json")) as f:
+        fixture = json.load(f)
+    R, Cn, nv = fixture["R"], fixture["C"], fixture["nv"]
+    assert (R, Cn, nv) == (96, 96, 3)
+    fields = [name for name, _ in _lib.XCall._fields_]
+    assert fixture["fields"] == fields  # every field of mvg_xcall is compared
+    keys = []
+    for alg in ("rowwise", "colwise", "blockwise"):
+        for G in (1, 2, 3, 4, 6, 8):
+            for exact in (False, True):
+                key = f"{alg}/G{G}/{'exact' if exact else 'tree'}"
+                keys.append(key)
+                cap = (16 * G + 16) * (nv + 1)
+                calls = (_lib.XCall * cap)()
+                n = C.c_int()
+                _lib.check(_lib.lib.mvg_debug_trace_exchange_multi(_lib.ALG_BY_NAME[alg], R, Cn, G, int(exact), nv, calls,
+                                                                   cap, C.byref(n)), "mvg_debug_trace_exchange_multi")
+                got = [[calls[i].as_dict()[f] for f in fields] for i in range(n.value)]
+                want = fixture["traces"][key]
+                assert len(got) == len(want), key
+                for i, (g, w) in enumerate(zip(got, want)):
+                    assert g == w, (key, i, dict(zip(fields, g)), dict(zip(fields, w)))
+    assert sorted(keys) == sorted(fixture["traces"])
+    assert all((len(fixture["traces"][k]) == 0) == ("/G1/" in k) for k in keys)
+    assert sum(len(t) for t in fixture["traces"].values()) == 452
+    # exact mode away from the row split: one combine per vector, after the gathers
+    for G in (2, 3, 4, 6, 8):
+        for alg in ("colwise", "blockwise"):
+            kinds = [c[1] for c in fixture["traces"][f"{alg}/G{G}/exact"]]
+            assert kinds.count(_lib.XCALL_COMBINE) == nv and kinds[-nv:] == [_lib.XCALL_COMBINE] * nv
+
+
 # ---------------------------------------------------------------- synthetic generator
 def test_synth_host_matches_oracle_bit_exact():
     A = mm.synth_host(37, 129, 42)
