@@ -57,6 +57,19 @@ inline int64_t short_row_piece_rows(int64_t k, int rows_per_block) {
     return cap / rows_per_block * rows_per_block;
 }
 
+// Rows [0, m) as consecutive ranges of at most max_rows rows, in order (each range is an
+// independent GEMV; max_rows: the caller's grid limit, and its short-row cap where it has one).
+// piece(r0, rows) launches one range and returns its status — the hipGetLastError after its
+// launch — and the first failure ends the walk and is returned.
+template <class F>
+int for_row_pieces(int64_t m, int64_t max_rows, F&& piece) {
+    for (int64_t r0 = 0; r0 < m; r0 += max_rows) {
+        const int rc = piece(r0, m - r0 < max_rows ? m - r0 : max_rows);
+        if (rc != MVG_OK) return rc;
+    }
+    return MVG_OK;
+}
+
 // ----- exact exchange (gemv_exact.hip): the reference's own combine orders on the root
 // MPI_Reduce(SUM) as the reference's MPICH runs it (colwise.c:124): binomial tree or, for long
 // buffers, reduce-scatter + gather, by MPICH 3.3.2's own rule (gemv_exact.hip); overwrites parts

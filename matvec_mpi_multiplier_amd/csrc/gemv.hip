@@ -769,8 +769,7 @@ static int launch(int v, const double* A, int64_t lda, const double* x, double* 
         const int64_t cap = short_row_piece_rows(K, var.rows_per_block);
         if (cap < max_rows) max_rows = cap;
     }
-    for (int64_t r0 = 0; r0 < M; r0 += max_rows) {
-        const int64_t m = M - r0 < max_rows ? M - r0 : max_rows;
+    return for_row_pieces(M, max_rows, [&](int64_t r0, int64_t m) {
         // row-pair forms: a last block of 2p rows with r < 2p rows left needs min(p, r) pairs,
         // more than ceil(r / 2); up to p = 16 spare workgroups cover it (theirs are rows >= m:
         // clamped loads, no store)
@@ -778,8 +777,8 @@ static int launch(int v, const double* A, int64_t lda, const double* x, double* 
         hipLaunchKernelGGL(var.fn, dim3((unsigned)blocks), dim3(var.threads), 0, s, A + r0 * lda, lda, x,
                            y + r0, m, K);
         MVG_HIP(hipGetLastError());
-    }
-    return MVG_OK;
+        return MVG_OK;
+    });
 }
 
 // ------------------------------------------------------------------ several x per pass
@@ -1835,13 +1834,14 @@ int mvg_gemv_multi_variant(const double* A, int64_t lda, const double* X, int64_
         const gemv_multi_fn fn = mv.fn16 ? mv.fn16 : mv.fn[slot];
         // launches of < 2^32 threads each (the grid-size cap), row ranges in order
         const int64_t max_rows = ((1ll << 31) / mv.block) * mv.rows_per_block;
-        for (int64_t r0 = 0; r0 < m; r0 += max_rows) {
-            const int64_t mm = m - r0 < max_rows ? m - r0 : max_rows;
+        const int rc = for_row_pieces(m, max_rows, [&](int64_t r0, int64_t mm) {
             const int64_t blocks = (mm + mv.rows_per_block - 1) / mv.rows_per_block;
             hipLaunchKernelGGL(fn, dim3((unsigned)blocks), dim3(mv.block), 0, s, A + r0 * lda, lda, Xg, ldx,
                                Yg + r0, ldy, mm, k, g);
             MVG_HIP(hipGetLastError());
-        }
+            return MVG_OK;
+        });
+        if (rc != MVG_OK) return rc;
     }
     return MVG_OK;
 }

@@ -469,7 +469,9 @@ constexpr int64_t kXlMaxK = 8192;  // x in LDS: up to 64 KiB per workgroup
 // column v of Y has the bits of gemv_seq_hop on x_v. The chains are independent, so their adds
 // interleave in the VALU while the A bytes are paid for once. These are siblings of hop_segment /
 // hop_masked_segment / hop_chain, not generalisations: the single-vector instantiations keep the
-// code, and the register allocation, they had.
+// code, and the register allocation, they had. One set of helpers at NV = 1 was tried form by
+// form (MEASUREMENTS §13): hipcc gives either the single-vector kernels or the NV ones their
+// loops and registers back, never both from one source.
 template <int L, int W, int NV, bool FWD>
 __device__ __forceinline__ void hop_segment_multi(double (&sum)[NV], const dbl2x (&a)[W / 2],
                                                   const dbl2x (&xv)[NV][W / 2]) {
@@ -874,8 +876,18 @@ static_assert(kSeqVariants[kHopRows].needs == kAnyOperands && kSeqVariants[kHopL
 // R x 60000: 1200 rows in 203 us, 679 with the LDS forms), 16 x 32 B for short ones. On rows
 // that start mid-line they beat the tree form itself (16384 x 16386: 305 us against 315);
 // config 5's shards and 4,194,304 x 512 run at 0.96-1.0 of the tree form's speed.
-// short rows (K <= 768) go out in launches of at most 1 GiB of A (mvg_gemv_exact_variant below)
+// short rows (K <= 768) go out in launches of at most 1 GiB of A (exact_piece_rows below)
 constexpr int64_t kShortRowK = 768;
+// Rows per launch of an exact form, single- or multi-vector (for_row_pieces, common.h): the
+// family's grid limit in whole workgroups, and for short rows at most 1 GiB of A, as the tree
+// form's one-row waves (gemv.hip): config 5's 16 GiB in 2.46 ms instead of 2.58, its 2 GiB shard
+// 316 against 318 us (round 3, profiles/r03/sublaunch/). The cap: short_row_piece_rows, common.h.
+static int64_t exact_piece_rows(int64_t k, int rows_per_block, int64_t max_blocks) {
+    const int64_t max_rows = max_blocks * rows_per_block;
+    if (k <= 0 || k > kShortRowK) return max_rows;
+    const int64_t cap = short_row_piece_rows(k, rows_per_block);
+    return cap < max_rows ? cap : max_rows;
+}
 constexpr int kMi355xCUs = 256;  // when no device answers (host-only callers, tests)
 //
 // Evenly placed 8-lane forms (round 4, profiles/r04/r4g, r4h): the 8-lane hop forms' one-wave
@@ -1106,38 +1118,36 @@ int mvg_gemv_exact_variant(const double* A, int64_t lda, const double* x, double
     if (var.xlds && k > kXlMaxK) return fail(MVG_E_INVALID, "mvg_gemv_exact: x-in-LDS variant needs k <= 8192");
     // k == 0 runs the kernel too: every row's sum stays 0 (the reference's `sum = 0`)
     // grid-size cap: fewer than 2^32 threads per launch
-    int64_t max_rows = ((1ll << 32) / (64 * var.waves) - 1) * var.rows;
-    // short rows (K <= 768): at most 1 GiB of A per launch, as the tree form's one-row waves
-    // (gemv.hip): config 5's 16 GiB in 2.46 ms instead of 2.58, its 2 GiB shard 316 against
-    // 318 us (round 3, profiles/r03/sublaunch/)
-    // (the cap: short_row_piece_rows, common.h)
-    if (k > 0 && k <= kShortRowK) {
-        const int64_t cap = short_row_piece_rows(k, var.rows);
-        if (cap < max_rows) max_rows = cap;
-    }
+    const int64_t max_rows = exact_piece_rows(k, var.rows, (1ll << 32) / (64 * var.waves) - 1);
     size_t lds = var.xlds ? (size_t)k * sizeof(double) : (size_t)var.lds_reserve;
     if (v == kHopEven)
         if (const int64_t o = g_even_lds_override.load(std::memory_order_relaxed); o > 0) lds = (size_t)o;
-    for (int64_t r0 = 0; r0 < m; r0 += max_rows) {
-        const int64_t mm = m - r0 < max_rows ? m - r0 : max_rows;
+    hipError_t refusal = hipSuccess;
+    const int rc = for_row_pieces(m, max_rows, [&](int64_t r0, int64_t mm) {
         const int rw = var.rows;
         hipLaunchKernelGGL(var.fn, dim3((unsigned)((mm + rw - 1) / rw)), dim3(64 * var.waves), lds, s,
                            A ? A + r0 * lda : A, lda, x, y + r0, mm, k);
         const hipError_t e = hipGetLastError();
-        // A runtime that turns down the evenly placed form's LDS reservation (the first launch of
-        // the call, nothing of it dispatched) gets the same sums from the one-wave form, and the
-        // dispatch keeps to the one-wave forms on this device from then on.
+        // the evenly placed form's LDS reservation turned down (the first launch of the call,
+        // nothing of it dispatched): not this call's failure, the walk ends for the retry below
         if (e != hipSuccess && variant == 0 && v == kHopEven && r0 == 0 && lds_refusal_confirmed(e, lds)) {
-            const int dev = current_device();
-            if (dev >= 0 && g_even_refused[dev].exchange(1, std::memory_order_relaxed) == 0)
-                fprintf(stderr, "matvec_gpu: device %d refused %zu B of LDS for the exact kernel's evenly placed form "
-                                "(%s); the exact dispatch keeps to the one-wave forms on it\n",
-                        dev, lds, hipGetErrorString(e));
-            return mvg_gemv_exact_variant(A, lda, x, y, m, k, kHopRows, stream);
+            refusal = e;
+            return MVG_E_HIP;
         }
         MVG_HIP(e);
+        return MVG_OK;
+    });
+    // A runtime that refused gets the same sums from the one-wave form, and the dispatch keeps to
+    // the one-wave forms on this device from then on.
+    if (refusal != hipSuccess) {
+        const int dev = current_device();
+        if (dev >= 0 && g_even_refused[dev].exchange(1, std::memory_order_relaxed) == 0)
+            fprintf(stderr, "matvec_gpu: device %d refused %zu B of LDS for the exact kernel's evenly placed form "
+                            "(%s); the exact dispatch keeps to the one-wave forms on it\n",
+                    dev, lds, hipGetErrorString(refusal));
+        return mvg_gemv_exact_variant(A, lda, x, y, m, k, kHopRows, stream);
     }
-    return MVG_OK;
+    return rc;
 }
 
 int mvg_gemv_exact_even_refused(int device) {
@@ -1209,20 +1219,16 @@ int mvg_gemv_exact_multi_variant(const double* A, int64_t lda, const double* X, 
         const int v = variant == 0 ? pick_seq_multi_variant(lda, ldx, m, k, nv - v0 >= 4 ? 4 : 2) : variant;
         const SeqMultiVariant& var = kSeqMultiVariants[v];
         if (!var.fn) break;
-        // launches of fewer than 2^31 threads; short rows (K <= 768) in pieces of at most 1 GiB of
-        // A, as the single-vector launch loop (mvg_gemv_exact_variant)
-        int64_t max_rows = ((1ll << 31) / 64 - 1) * var.rows;
-        if (k <= kShortRowK) {
-            const int64_t cap = short_row_piece_rows(k, var.rows);
-            if (cap < max_rows) max_rows = cap;
-        }
+        // launches of fewer than 2^31 threads
+        const int64_t max_rows = exact_piece_rows(k, var.rows, (1ll << 31) / 64 - 1);
         const int g = nv - v0 < var.nv ? nv - v0 : var.nv;
-        for (int64_t r0 = 0; r0 < m; r0 += max_rows) {
-            const int64_t mm = m - r0 < max_rows ? m - r0 : max_rows;
+        const int rc = for_row_pieces(m, max_rows, [&](int64_t r0, int64_t mm) {
             hipLaunchKernelGGL(var.fn, dim3((unsigned)((mm + var.rows - 1) / var.rows)), dim3(64), 0, (hipStream_t)stream,
                                A + r0 * lda, lda, X + v0 * ldx, ldx, Y + v0 * ldy + r0, ldy, mm, k, g);
             MVG_HIP(hipGetLastError());
-        }
+            return MVG_OK;
+        });
+        if (rc != MVG_OK) return rc;
         v0 += g;
     }
     // per vector (k == 0 included: every row's sum stays 0)

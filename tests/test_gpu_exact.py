@@ -70,22 +70,63 @@ def test_gemv_exact_hop_segment_edges():
     # number in lane 0, so every variant is run with odd and even segment counts, with and
     # without leftover segments (nseg % U), a column tail, no whole segment at all, and a
     # last wave with rows to spare
+    #
+    # and with the K list of the several-vector forms' test (test_gpu_exact_multi.py): the head
+    # alone, no main segment, the drain alone, exactly one group, a group and a drain, two groups,
+    # with 0, 1 and 2 masked tails — each K on every layout the form accepts:
+    #   tight        lda = K (the 16-B forms where K is even)
+    #   lines        A on a 128-B line, lda a multiple of 16: no head, K / S main segments
+    #   mid_line     lda = K + 13: every row its own head (8-B forms)
+    #   even_lda     lda = K + 14 where K is even (16-B forms)
+    #   off_8_bytes  A and x 8 bytes past the lines layout's (8-B forms)
+    # Padding columns hold NaN (no form may read them into a sum). One A, x and reference per K,
+    # made for the tallest form; a form with fewer rows takes the first m (a row's chain does not
+    # depend on the others).
+    users = {}  # K -> [(variant, name, m)]
     for v, name in exact_variants():
         if not name.startswith("hop"):
             continue
         L, W, U = (int(part[1:]) for part in name.split("_")[1:4])
-        nw = int(name.split("_n")[-1]) if xl_k_limited(name) else 1  # waves per workgroup
+        nw = int(name.split("_n")[-1]) if "_n" in name else 1  # waves per workgroup
         S = L * W
         m = 3 * nw * (64 // L) + 1
         ks = [S - 2, S, 3 * S + 2, (U + 1) * S, (U + 1) * S + 2, (U + 2) * S, 2 * U * S, 2 * U * S + 2,
               (3 * U - 1) * S]
         if not needs_16b(name):  # odd widths too: every other row starts 8 bytes off a 16-B boundary
             ks += [k + 1 for k in ks]
-        for k in ks:
-            A = signed(oracle.synth(m, k, 42), k)
-            x = signed(oracle.synth(1, k, 4242)[0], k + 1)
-            y = mm.multiply_std_rowwise(A, x, variant=v, exact=True)
-            assert np.array_equal(y, oracle.multiply_std_rowwise(A, x)), (name, m, k)
+        ks += [0, 1, 15, 16, S - 1, S, S + 15, U * S, U * S + 1, (U + 1) * S + 15, (2 * U + 1) * S + 17]
+        for k in set(ks):
+            users.setdefault(k, []).append((v, name, m))
+    m_max = max(m for forms in users.values() for _, _, m in forms)
+    dy = mm.DeviceBuffer(m_max)
+    launches = 0
+    for k, forms in sorted(users.items()):
+        A = signed(oracle.synth(m_max, k, 42), k) if k else np.zeros((m_max, 0))
+        x = signed(oracle.synth(1, k, 4242)[0], k + 1) if k else np.zeros(0)
+        want = oracle.multiply_std_rowwise(A, x) if k else np.zeros(m_max)
+        lined = (k // 16 + 1) * 16
+        for label, lda, shift, wide in (("tight", k, 0, None), ("lines", lined, 0, None), ("mid_line", k + 13, 0, False),
+                                        ("even_lda", k + 14, 0, True), ("off_8_bytes", lined, 1, False)):
+            lda = max(lda, 1)
+            takers = [f for f in forms if wide is None or needs_16b(f[1]) == wide]
+            takers = [f for f in takers if not (needs_16b(f[1]) and lda % 2)]
+            if not takers:
+                continue
+            image = np.full((m_max, lda), np.nan)
+            image[:, :k] = A
+            dA = mm.DeviceBuffer(image.size + shift).upload(np.concatenate([np.full(shift, np.nan), image.ravel()]))
+            dx = mm.DeviceBuffer(k + shift).upload(np.concatenate([np.full(shift, np.nan), x]))
+            for v, name, m in takers:
+                dy.upload(np.full(m_max, np.nan))
+                mm.gemv(dA.ptr + 8 * shift, lda, dx.ptr + 8 * shift, dy.ptr, m, k, None, v, exact=True)
+                _lib.check(_lib.lib.mvg_stream_sync(None), "sync")
+                y = dy.download()
+                assert np.array_equal(y[:m], want[:m]) and np.isnan(y[m:]).all(), (name, label, m, k, lda)
+                launches += 1
+            dA.free()
+            dx.free()
+    dy.free()
+    assert launches > 1000  # every form on every layout it accepts
 
 
 def test_gemv_exact_rows_beyond_lds_offsets():
