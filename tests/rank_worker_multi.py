@@ -11,6 +11,12 @@ data, so the order of summation shows in the bits; the block split at 3 grid col
 rank order), <= 1e-12 relative in tree mode on the generator's non-negative values. Then, once per
 algorithm on the first shape, the checks named in EXTRAS.
 
+Here every load() follows a collect_multi, so it starts on idle streams. Everything
+sequence-shaped — blocks in flight with different A and X, both kinds of multiply around the
+ring, a block that grows with exchanges pending, chunked distribution, lowered root-send staging,
+panel shards, 3 ranks — is walked by the op-sequence scripts instead (BLOCK_RUNS and
+BLOCK_PANEL_RUNS in tests/engine_scripts.py, tests/test_gpu_engine_block_sequences.py).
+
 Every rank prints one JSON line per check and a last line {"done": true, ...}. A failed check is
 recorded and the rank walks on, so no peer is left inside a collective; the exit status is 1 if any
 check of this rank failed.

@@ -1,5 +1,5 @@
-"""Worker for tests/test_gpu_engine_sequences.py (run under torch.distributed.run; not collected
-by pytest).
+"""Worker for tests/test_gpu_engine_sequences.py and tests/test_gpu_engine_block_sequences.py
+(run under torch.distributed.run; not collected by pytest).
 
 One process per rank, every rank on GPU 0 (a distinct NCCL_HOSTID per rank and loopback sockets,
 as tests/rank_worker_b2b.py). One launch walks every case of its kind, all three algorithms
@@ -8,6 +8,9 @@ as tests/rank_worker_b2b.py). One launch walks every case of its kind, all three
   small             every script of engine_scripts.SMALL_RUNS at the small shapes
   panels [alg ...]  engine_scripts.PANEL_RUNS at the panel shapes (world 2), all algorithms or
                     the named ones
+  blocks [alg ...]  every script of engine_scripts.BLOCK_RUNS (a block of vectors beside the
+                    single one) at the small shapes, all algorithms or the named ones
+  blockpanels [alg ...]  engine_scripts.BLOCK_PANEL_RUNS at the panel shapes (world 2)
 
 Every rank prints one JSON line per (case, check), and a last line {"done": true, ...}. A failed
 check is recorded and the rank walks on, so no peer is left inside a collective; the exit status
@@ -47,6 +50,10 @@ def main():
         shapes, runs, keep = ES.small_shapes(), ES.SMALL_RUNS, 64
     elif kind == "panels":
         shapes, runs, keep = ES.panel_shapes(tuple(sys.argv[2:]) or ES.ALGS), ES.PANEL_RUNS, 6
+    elif kind == "blocks":
+        shapes, runs, keep = ES.small_shapes(tuple(sys.argv[2:]) or ES.ALGS), ES.BLOCK_RUNS, 64
+    elif kind == "blockpanels":
+        shapes, runs, keep = ES.panel_shapes(tuple(sys.argv[2:]) or ES.ALGS), ES.BLOCK_PANEL_RUNS, 6
     else:
         raise SystemExit(f"unknown kind {kind!r}")
     t0 = time.perf_counter()

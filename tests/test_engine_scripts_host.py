@@ -9,13 +9,14 @@ import numpy as np
 import pytest
 
 import engine_scripts as ES
-from engine_scripts import D, F, M, O, S, T, X, Y  # noqa: F401
+from engine_scripts import CM, D, F, G, M, MM, O, S, T, V, X, Y  # noqa: F401
 from matvec_mpi_multiplier_amd import _lib
 from matvec_mpi_multiplier_amd import multiplier as mm
 from oracle import oracle
 
 lib = _lib.lib
-ALL_RUNS = [(n, r) for n, r in ES.SMALL_RUNS.items()] + [("panel/" + n, r) for n, r in ES.PANEL_RUNS.items()]
+ALL_RUNS = ([(n, r) for n, r in ES.SMALL_RUNS.items()] + [("panel/" + n, r) for n, r in ES.PANEL_RUNS.items()]
+            + [(n, r) for n, r in ES.BLOCK_RUNS.items()] + [("panel/" + n, r) for n, r in ES.BLOCK_PANEL_RUNS.items()])
 
 
 # ------------------------------------------------------------------ the scripts
@@ -23,9 +24,12 @@ ALL_RUNS = [(n, r) for n, r in ES.SMALL_RUNS.items()] + [("panel/" + n, r) for n
 def test_every_script_is_well_formed(name, run):
     script = run[0]
     assert ES.well_formed(script), ES.spell(script)
-    assert sum(op == ES.C for op in script) >= 1
+    assert sum(op == ES.C for op in script) >= 1 or sum(op == CM for op in script) >= 1
     writes = [op[1] for op in script if op[0] in ES.WRITES]
     assert len(writes) == len(set(writes))  # every write brings a data set no earlier one did
+    vsets = [op[1] for op in script if op[0] in ES.VECTORS]
+    assert len(vsets) == len(set(vsets))    # and every V or G a vector set no earlier one did
+    assert max(writes + vsets) < ES.SET_STRIDE  # join() keeps the scripts of a group apart
 
 
 def test_well_formed_rejects_what_it_must():
@@ -265,6 +269,7 @@ class FakeEngine:
         self.panelP, self.dAp, self.panels_fresh, self.uses, self.chunks_pending = 0, False, False, 0, False
         self.overlap, self.timing, self.launches = 0, 0, 0
         self.sets, self.y_set, self.calls = [], None, []
+        self.vsets, self.vectors, self.Y_of = [], 0, None
 
     def shard(self, i=0):
         return self.plan
@@ -337,6 +342,43 @@ class FakeEngine:
         if self.fault == "one_ulp":
             y[0] = np.nextafter(y[0], np.inf)
         return y
+
+    # ---- the block: X is told apart by identity, as A is; Y is the oracle's of what the last
+    # multiply_multi saw. `fault`: "mm_uses" counts it as a use of A, "mm_timed" times it,
+    # "mm_keeps_chunks" leaves a chunked distribution pending, "stale_x" multiplies the vector
+    # set before the current one
+    def set_vectors(self, Xm, nv=None):
+        assert (Xm is None) == (self.rank != 0)  # X on the root alone
+        if Xm is not None:
+            assert Xm.shape == (self.C, nv) and Xm.T.flags.c_contiguous  # handed over without a copy
+            j = next(j for j in range(80) if np.shares_memory(Xm, self.data.vectors("V", j)))
+        self.vsets.append(("V", j if Xm is not None else -1, nv))
+        self.vectors = nv
+
+    def fill_synth_vectors(self, seed, nv):
+        self.vsets.append(("G", (seed - 777) // 2, nv))
+        assert ES.seed_of(self.vsets[-1][1]) == seed
+        self.vectors = nv
+
+    def multiply_multi(self):
+        self.calls.append("MM")
+        if self.fault == "mm_uses":
+            self.uses += 1
+        if self.fault == "mm_timed" and self.timing == 1:
+            self.launches += 1
+        if self.fault != "mm_keeps_chunks":
+            self.chunks_pending = False
+        vset = self.vsets[-2] if self.fault == "stale_x" and len(self.vsets) > 1 else self.vsets[-1]
+        self.Y_of = (self.sets[-1], vset[:2] + (self.vsets[-1][2],))
+
+    def collect_multi(self):
+        self.calls.append("CM")
+        if self.rank:
+            return None
+        Yb = self.data.want_multi(self.name, self.world, *self.Y_of)[0].copy()
+        if self.fault == "one_ulp":
+            Yb[0, -1] = np.nextafter(Yb[0, -1], np.inf)
+        return Yb
 
 
 @pytest.mark.parametrize("name,run", list(ES.SMALL_RUNS.items()), ids=list(ES.SMALL_RUNS))
@@ -459,3 +501,299 @@ def test_set_stage_elems_hook():
         assert len(pieces("rowwise", 240, 3072, 2, 1, 0)[1]) == 2
     finally:
         assert lib.mvg_debug_set_stage_elems(0) == _lib.MVG_OK
+
+
+# ------------------------------------------------------------------ a block of vectors beside the single one
+def test_well_formed_rejects_ill_formed_block_scripts():
+    assert ES.well_formed((D(0), V(0, 3), MM, CM))
+    assert not ES.well_formed((V(0, 3), MM, CM))                        # no write of A before the MM
+    assert not ES.well_formed((D(0), MM, CM))                           # no V or G before the MM
+    assert not ES.well_formed((D(0), V(0, 3), CM))                      # a CM with no MM before it
+    assert not ES.well_formed((D(0), V(0, 3), M, CM))                   # an M is no MM
+    assert not ES.well_formed((D(0), V(0, 3), MM, ES.C))                # and an MM no M
+    assert not ES.well_formed((D(0), V(0, 3), MM, V(1, 3), CM))         # a V between the MM and its CM
+    assert not ES.well_formed((D(0), V(0, 3), MM, G(1, 3), CM))         # a G
+    assert not ES.well_formed((D(0), V(0, 3), MM, S(1), CM))            # a write of A
+    assert not ES.well_formed((D(0), V(0, 3), MM, CM, G(0, 3), MM, CM))  # a vector set used twice
+    assert not ES.well_formed((D(0), V(0, 4), MM, CM))                  # nv outside NVS
+    assert ES.well_formed((D(0), V(0, 3), MM, M, X(0), CM, ES.C))       # an M or a mode leaves Y as it is
+    assert ES.NVS == (1, 3, 7, 11) and ES.NV_MAX == 11 and ES.seed_of(0) == 777
+
+
+def test_the_block_scripts_are_the_ones_agreed():
+    assert ES.spell(ES.BLK_B2B_EXACT) == "X1 D0 V0:3 MM D1 V1:3 MM D2 V2:3 MM CM"
+    assert ES.spell(ES.BLK_MIXED_RING) == ("D0 V0:7 M MM M MM M MM M MM M MM C CM "
+                                           "X1 D1 V1:3 MM M MM M MM M MM M MM M CM C")
+    assert ES.spell(ES.BLK_GROW_IN_FLIGHT) == "D0 V0:3 MM MM MM V1:11 MM CM V2:1 MM CM X1 MM CM G3:7 MM CM"
+    assert ES.spell(ES.BLK_CHUNKED) == ("X1 O3 S0 V0:7 MM CM M C O7 S1 S2 MM CM S3 M MM C CM O0 S4 MM CM D5 MM CM")
+    assert ES.spell(ES.BLK_TIMED_CHUNKS) == "O3 T1 S0 V0:3 MM M C S1 M C MM CM T0"
+    assert ES.spell(ES.BLK_SEND_PIECES) == "D0 V0:11 MM D1 V1:11 MM CM X1 D2 MM M CM C"
+    assert ES.spell(ES.BLK_WRITERS) == ("F0 G0:7 MM CM S1 V1:3 MM CM D2 G2:11 MM CM V3:11 MM CM X1 F3 MM CM G4:3 MM CM "
+                                        "S4 V5:7 MM CM D5 MM CM G6:1 V7:1 MM CM")
+    assert ES.spell(ES.BLOCK_PANEL_RUNS["blk_panels"][0]) == "X1 S0 V0:3 M M C MM CM S1 MM CM M C M C MM CM X0 MM CM"
+    assert ES.spell(ES.BLOCK_PANEL_RUNS["blk_chunked"][0]).endswith("O0 S4 MM CM S5 MM CM")
+    rings = {n: r[1]["MVG_XRING"] for n, r in ES.BLOCK_RUNS.items() if "/ring" in n}
+    assert rings == {f"{s}/ring{n}": str(n) for s, ns in (("blk_b2b_exact", (1, 2, 8)), ("blk_b2b_again", (1, 2, 8)),
+                                                          ("blk_mixed_ring", (2, 3, 8))) for n in ns}
+    assert all(ES.BLOCK_RUNS[f"blk_b2b_again/ring{n}"][0] is ES.BLK_B2B_EXACT for n in (1, 2, 8))
+    assert [n for n, r in ES.BLOCK_RUNS.items() if r[2]] == ["blk_send_pieces"]
+    assert ES.BLOCK_RUNS["blk_send_pieces"][2] == ES.SEND_PIECES_STAGE
+    assert all(r[1] == {"MVG_NO_PANELS": "0"} for r in ES.BLOCK_PANEL_RUNS.values())
+    # V and G follow one another both ways round, and every writer of A comes before an MM in
+    # both modes
+    w = ES.spell(ES.BLK_WRITERS)
+    assert "G6:1 V7:1" in w and w.index("G2:11") < w.index("V3:11") < w.index("G4:3")
+    tree, exact = w.split(" X1 ")
+    assert all(k in tree and k in exact for k in "FSD")
+
+
+def block_answers(script, alg, R, Cn, world, rank, no_panels=False):
+    """[(set, vset or None at a C, exact, width, launches)] per C and CM."""
+    return [("%s%d" % m["set"], "%s%d:%d" % m["vset"] if "vset" in m else None, m["exact"], m["width"], m["launches"])
+            for m in ES.expect(script, alg, R, Cn, world, rank, no_panels)]
+
+
+def test_block_model_literal_small_shape_colwise_world_2():
+    R, Cn = 1200, 960
+    for rank in (0, 1):
+        def got(s):
+            return block_answers(s, "colwise", R, Cn, 2, rank)
+
+        assert got(ES.BLK_B2B_EXACT) == [("D2", "V2:3", True, 0, None)]
+        assert got(ES.BLK_MIXED_RING) == [("D0", None, False, 0, None), ("D0", "V0:7", False, 0, None),
+                                          ("D1", "V1:3", True, 0, None), ("D1", None, True, 0, None)]
+        # set, vector set and mode are the last MM's: V2:1 is still current at the exact MM
+        assert got(ES.BLK_GROW_IN_FLIGHT) == [("D0", "V1:11", False, 0, None), ("D0", "V2:1", False, 0, None),
+                                              ("D0", "V2:1", True, 0, None), ("D0", "G3:7", True, 0, None)]
+        assert got(ES.BLK_CHUNKED) == [("S0", "V0:7", True, 0, None), ("S0", None, True, 0, None),
+                                       ("S2", "V0:7", True, 0, None), ("S3", None, True, 0, None),
+                                       ("S3", "V0:7", True, 0, None), ("S4", "V0:7", True, 0, None),
+                                       ("D5", "V0:7", True, 0, None)]
+        # S0 MM M: the MM consumed the chunks, so the M is whole and timed; S1 M: chunked, not
+        # timed; the MM after it is never timed
+        assert got(ES.BLK_TIMED_CHUNKS) == [("S0", None, False, 0, 1), ("S1", None, False, 0, 1),
+                                            ("S1", "V0:3", False, 0, 1)]
+        assert got(ES.BLK_SEND_PIECES) == [("D1", "V1:11", False, 0, None), ("D2", "V1:11", True, 0, None),
+                                           ("D2", None, True, 0, None)]
+        assert got(ES.BLK_WRITERS) == [
+            ("F0", "G0:7", False, 0, None), ("S1", "V1:3", False, 0, None), ("D2", "G2:11", False, 0, None),
+            ("D2", "V3:11", False, 0, None), ("F3", "V3:11", True, 0, None), ("F3", "G4:3", True, 0, None),
+            ("S4", "V5:7", True, 0, None), ("D5", "V5:7", True, 0, None), ("D5", "V7:1", True, 0, None)]
+    # the pair the model's second rule rests on: without the MM the M consumes the chunks untimed
+    assert [a[4] for a in block_answers((O(3), T(1), S(0), V(0, 3), MM, M, ES.C), "colwise", R, Cn, 2, 0)] == [1]
+    assert [a[4] for a in block_answers((O(3), T(1), S(0), M, ES.C), "colwise", R, Cn, 2, 0)] == [0]
+
+
+def test_block_model_literal_panel_shape_colwise_world_2():
+    R, Cn = ES.panel_shape("colwise")
+    for rank in (0, 1):
+        # 256 only where two M have run since the last write; no MM moves the width, beside a
+        # fresh copy (checks 1, 5), a stale one (2) and after X0 released it (6)
+        assert block_answers(ES.BLOCK_PANEL_RUNS["blk_panels"][0], "colwise", R, Cn, 2, rank) == [
+            ("S0", None, True, 256, None), ("S0", "V0:3", True, 256, None), ("S1", "V0:3", True, 0, None),
+            ("S1", None, True, 0, None), ("S1", None, True, 256, None), ("S1", "V0:3", True, 256, None),
+            ("S1", "V0:3", False, 0, None)]
+        # no set is multiplied by M twice
+        assert block_answers(ES.BLOCK_PANEL_RUNS["blk_chunked"][0], "colwise", R, Cn, 2, rank) == [
+            ("S0", "V0:7", True, 0, None), ("S0", None, True, 0, None), ("S2", "V0:7", True, 0, None),
+            ("S3", None, True, 0, None), ("S3", "V0:7", True, 0, None), ("S4", "V0:7", True, 0, None),
+            ("S5", "V0:7", True, 0, None)]
+        # an MM between the two M is no use: S0 M MM M builds at the second M, S0 M MM does not
+        assert [a[3] for a in block_answers((X(1), S(0), V(0, 3), M, MM, CM, M, ES.C), "colwise", R, Cn, 2, rank)] == [0, 256]
+        assert [a[3] for a in block_answers((X(1), S(0), V(0, 3), MM, M, MM, CM), "colwise", R, Cn, 2, rank)] == [0]
+
+
+def test_block_scripts_that_share_an_engine_keep_their_own_answers():
+    assert [g[0] for g in ES.groups(ES.BLOCK_RUNS)] == [
+        ["blk_b2b_exact/ring1", "blk_b2b_again/ring1"],
+        ["blk_mixed_ring/ring2", "blk_b2b_exact/ring2", "blk_b2b_again/ring2"],
+        ["blk_mixed_ring/ring3"],
+        ["blk_mixed_ring/ring8", "blk_b2b_exact/ring8", "blk_b2b_again/ring8", "blk_grow_in_flight", "blk_chunked",
+         "blk_timed_chunks", "blk_writers"],
+        ["blk_send_pieces"]]
+    assert [g[0] for g in ES.groups(ES.BLOCK_PANEL_RUNS)] == [["blk_panels", "blk_chunked"]]
+    for runs, shape, world in ((ES.BLOCK_RUNS, (1200, 960), 2), (ES.BLOCK_RUNS, (240, 3072), 1),
+                               (ES.BLOCK_PANEL_RUNS, ES.panel_shape("colwise"), 2)):
+        for names, env, stage in ES.groups(runs):
+            script, owners = ES.join(names, runs)
+            assert ES.well_formed(script)
+            assert owners == [(n, c) for n in names for c in range(ES.n_checks(runs[n][0]))]
+            for rank in range(world):
+                joined = ES.expect(script, "colwise", *shape, world, rank)
+                alone = []
+                for k, n in enumerate(names):
+                    for m in ES.expect(runs[n][0], "colwise", *shape, world, rank):
+                        m = dict(m, set=(m["set"][0], m["set"][1] + ES.SET_STRIDE * k))
+                        if "vset" in m:
+                            m["vset"] = (m["vset"][0], m["vset"][1] + ES.SET_STRIDE * k, m["vset"][2])
+                        alone.append(m)
+                assert joined == alone, names
+
+
+def ring_group(ring):
+    """The scripts that walk the engine of ring length `ring`, joined as the runner walks them."""
+    names = next(g[0] for g in ES.groups(ES.BLOCK_RUNS) if g[1] == {"MVG_XRING": str(ring)} and g[2] == 0)
+    script, owners = ES.join(names, ES.BLOCK_RUNS)
+    return names, script
+
+
+def multiplies_of(names, script, name):
+    """ES.slots' entries of the multiplies that script `name` of the group issues."""
+    per = {n: sum(op[0] in ("M", "MM") for op in ES.BLOCK_RUNS[n][0]) for n in names}
+    start = sum(per[n] for n in names[:names.index(name)])
+    return ES.slots(script, int(ES.BLOCK_RUNS[name][1]["MVG_XRING"]))[start:start + per[name]]
+
+
+@pytest.mark.parametrize("ring", [2, 3, 8])
+def test_mixed_ring_takes_the_ring_wait_on_either_kind_behind_the_other(ring):
+    names, script = ring_group(ring)
+    assert names[0] == f"blk_mixed_ring/ring{ring}"  # the engine's first script: its slots count from 0
+    walked = multiplies_of(names, script, names[0])
+    # each half issues more multiplies than the ring has slots, the second the other kind first
+    assert [w[0] for w in walked] == ["M", "MM"] * 5 + ["MM", "M"] * 5 and 10 > ring
+    # slot 0 with an exchange pending (the wait is taken) on an MM right behind an M's exchange ...
+    assert any(w == ("MM", 0, "M", True) for w in walked), walked
+    # ... and on an M right behind an MM's
+    assert any(w == ("M", 0, "MM", True) for w in walked), walked
+
+
+def test_b2b_walks_end_in_different_slots():
+    for ring, ends in ((2, (0, 1)), (8, (6, 1))):
+        names, script = ring_group(ring)
+        first = multiplies_of(names, script, f"blk_b2b_exact/ring{ring}")
+        again = multiplies_of(names, script, f"blk_b2b_again/ring{ring}")
+        assert [w[0] for w in first + again] == ["MM"] * 6
+        assert (first[-1][1], again[-1][1]) == ends  # the Y that is checked comes out of another slot
+    # a ring of one exchanges on the GEMV stream: one slot, no wait
+    names, script = ring_group(1)
+    assert all(w[1:] == (0, p, False) for w, p in zip(ES.slots(script, 1), [None] + ["MM"] * 5))
+
+
+def test_slot_replay_follows_the_engine():
+    s = (D(0), V(0, 1), M, MM, Y, M, M, T(1), MM, ES.C, MM, T(0), M)
+    assert ES.slots(s, 2) == [("M", 0, None, False), ("MM", 1, "M", False), ("M", 0, "MM", False), ("M", 1, "M", False),
+                              ("MM", 0, "M", False), ("MM", 1, "MM", False), ("M", 0, "MM", False)]
+    assert ES.slots((D(0), M, M, M, ES.C, M, M), 2) == [("M", 0, None, False), ("M", 1, "M", False), ("M", 0, "M", True),
+                                                       ("M", 1, "M", False), ("M", 0, "M", True)]
+
+
+@pytest.mark.parametrize("R,Cn", ES.SMALL_SHAPES)
+def test_signed_vector_sets_separate_the_combine_orders(R, Cn):
+    """test_signed_sets_separate_the_column_splits_orders and its block-split twin, for the
+    vectors of the V sets: an exact-mode pass of a block proves the combine order per vector only
+    if another order would give other bits. Every V set of the scripts (j below SET_STRIDE + 3:
+    the second walk of blk_b2b_exact included), its first and last vector, on a signed A."""
+    data = ES.DataSets(R, Cn)
+    A = data.inputs("D", 0)[0]
+    for j in list(range(8)) + [10, 11, 12]:
+        XT = data.vectors("V", j)
+        assert XT.shape == (ES.NV_MAX, Cn) and XT.flags.c_contiguous
+        assert np.array_equal(np.abs(XT), data.vectors("G", j))  # the same values, signs apart
+        assert np.array_equal(data.vectors("G", j), oracle.synth(ES.NV_MAX, Cn, 777 + 2 * j))
+        for v in (0, ES.NV_MAX - 1):
+            x = XT[v]
+            assert (x < 0).any() and (x > 0).any()
+            for P in (3, 4, 6):
+                parts = colwise_parts(A, x, P)
+                want = oracle.multiply("colwise", A, x, P)
+                other = parts[0] + (parts[1] + parts[2]) if P == 3 else in_order(parts)
+                assert np.count_nonzero(other != want) >= R // 8, (j, v, P)
+            want = oracle.multiply("blockwise", A, x, 6)
+            back = np.zeros(R)
+            for r in (5, 4, 3, 2, 1, 0):
+                sh = mm.plan_shard("blockwise", R, Cn, 6, r)
+                blk = np.ascontiguousarray(A[sh.row_off:sh.row_off + sh.n_rows, sh.col_off:sh.col_off + sh.n_cols])
+                rows = slice(sh.y_off, sh.y_off + sh.y_len)
+                back[rows] = back[rows] + oracle.multiply_std_rowwise(blk, x[sh.col_off:sh.col_off + sh.n_cols])
+            assert np.count_nonzero(back != want) >= R // 8, (j, v)
+
+
+def test_every_two_vector_sets_differ_everywhere():
+    # a Y from any other vector set of a script, or from the neighbouring column, misses the bound
+    # in (nearly) every element
+    R, Cn = 240, 3072
+    data = ES.DataSets(R, Cn)
+    ys = {(k, j): data.want_multi("colwise", 2, ("D", 0), (k, j, 3)) for k in "VG" for j in range(4)}
+    for a in ys:
+        for b in ys:
+            if a != b:
+                assert np.count_nonzero(np.abs(ys[a][0] - ys[b][0]) > ES.TOL * ys[b][1]) >= 3 * R - 6, (a, b)
+    want, mag = ys["V", 0]
+    assert np.count_nonzero(np.abs(want[:, 0] - want[:, 1]) > ES.TOL * mag[:, 1]) >= R - 2
+    # a column is the single vector's product of that vector
+    A, XT = data.inputs("D", 0)[0], data.vectors("V", 0)
+    assert np.array_equal(want[:, 2], oracle.multiply("colwise", A, XT[2], 2))
+    assert np.array_equal(mag[:, 2], np.abs(A) @ np.abs(XT[2]))
+
+
+def test_checker_takes_a_block():
+    R, Cn = 240, 3072
+    data = ES.DataSets(R, Cn)
+    want, mag = data.want_multi("colwise", 3, ("D", 0), ("V", 0, 7))
+    assert want.shape == mag.shape == (R, 7)
+    assert ES.check_y(want.copy(), want, mag, True) == (True, 0.0)
+    one = want.copy()
+    one[5, 6] = np.nextafter(one[5, 6], np.inf)
+    assert ES.check_y(one, want, mag, True) == (False, 1.0) and ES.check_y(one, want, mag, False)[0]
+    off = want.copy()
+    off[7, 3] += 2e-12 * mag[7, 3]
+    ok, figure = ES.check_y(off, want, mag, False)
+    assert not ok and 1.5e-12 < figure < 2.5e-12
+    assert not ES.check_y(want[:, :6], want, mag, False)[0]              # a column short
+    assert not ES.check_y(want[:, ::-1].copy(), want, mag, False)[0]     # the columns in another order
+
+
+BLOCK_SCRIPTS = [(n, r) for n, r in ES.BLOCK_RUNS.items() if "again" not in n and n.split("/")[-1] not in ("ring3", "ring8")]
+
+
+@pytest.mark.parametrize("name,run", BLOCK_SCRIPTS, ids=[n for n, _ in BLOCK_SCRIPTS])
+def test_runner_walks_the_block_scripts_and_records_a_wrong_engine(name, run):
+    R, Cn = 240, 3072
+    data = ES.DataSets(R, Cn)
+    script = run[0]
+    n = ES.n_checks(script)
+    blocks = [i for i, m in enumerate(ES.expect(script, "colwise", R, Cn, 3, 0)) if "vset" in m]
+    for alg, world in (("colwise", 3), ("blockwise", 6), ("rowwise", 1)):
+        for rank in {0, world - 1}:
+            e = FakeEngine(alg, R, Cn, world, rank, data)
+            recs = ES.run_script(e, script, data, world)
+            assert len(recs) == n and all(r["ok"] for r in recs), recs
+            assert all((r["y_ok"] is None) == (rank != 0) for r in recs)
+            assert [c for c in e.calls if c in ("M", "MM", "C", "CM")] == [op[0] for op in script if op[0] in ("M", "MM", "C", "CM")]
+        # one ulp in one element of Y: caught exactly where the model says exact mode is on
+        recs = ES.run_script(FakeEngine(alg, R, Cn, world, 0, data, fault="one_ulp"), script, data, world)
+        assert [r["ok"] for r in recs] == [not r["want_exact"] for r in recs]
+        # the vector set before the current one: every CM after the script's second V or G is wrong
+        recs = ES.run_script(FakeEngine(alg, R, Cn, world, 0, data, fault="stale_x"), script, data, world)
+        first = next(op for op in script if op[0] in ES.VECTORS)
+        later = [recs[i] for i in blocks if recs[i]["vset"] != "%s%d:%d" % first]
+        assert not any(r["ok"] or r["y_ok"] for r in later), later
+        assert len(recs) == n
+
+
+def test_runner_catches_a_block_that_counts_is_timed_or_leaves_the_chunks():
+    class NoData:
+        token = np.zeros(1)
+
+        def inputs(self, kind, i):
+            return self.token, self.token
+
+        def vectors(self, kind, j):
+            return None
+
+    # off the root the stand-in never looks at values: widths and launches alone
+    alg = "colwise"
+    R, Cn = ES.panel_shape(alg)
+    panels = ES.BLOCK_PANEL_RUNS["blk_panels"][0]
+    for fault, want_ok in ((None, True), ("mm_uses", False)):
+        recs = ES.run_script(FakeEngine(alg, R, Cn, 2, 1, NoData(), fault=fault), panels, NoData(), 2)
+        assert all(r["ok"] for r in recs) == want_ok
+        assert [r["want_width"] for r in recs] == [256, 256, 0, 0, 256, 256, 0]
+        if fault:  # S1 MM CM M C: the MM counted, so the first M already builds the copy
+            assert [r["width"] for r in recs] == [256, 256, 0, 256, 256, 256, 0]
+    for fault, launches in ((None, [1, 1, 1]), ("mm_timed", [2, 2, 3]), ("mm_keeps_chunks", [0, 0, 0])):
+        recs = ES.run_script(FakeEngine(alg, 1200, 960, 2, 1, NoData(), fault=fault), ES.BLK_TIMED_CHUNKS, NoData(), 2)
+        assert [r["want_launches"] for r in recs] == [1, 1, 1]
+        assert [r["launches"] for r in recs] == launches
+        assert all(r["ok"] for r in recs) == (fault is None)
+

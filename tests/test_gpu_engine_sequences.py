@@ -45,7 +45,7 @@ FAULT = re.compile(r"exitcode\s*:\s*-(?!15\b)\d+|Signal (?!15\b)\d+|core dumped|
 
 
 def n_checks(name, runs):
-    return sum(op == ES.C for op in runs[name][0])
+    return ES.n_checks(runs[name][0])
 
 
 def report(key, lines, secs):
@@ -58,7 +58,7 @@ def report(key, lines, secs):
     print(f"engine sequences {key}: {secs:.1f} s wall, {len(per)} scripts, slowest {slow}")
 
 
-def run_world_1(always_collect):
+def run_world_1(always_collect, runs=ES.SMALL_RUNS):
     from matvec_mpi_multiplier_amd import multiplier as mm
 
     lines = []
@@ -66,7 +66,7 @@ def run_world_1(always_collect):
     with ES.environment({"MVG_ALWAYS_COLLECT": "1" if always_collect else "0"}):
         comm = mm.Comm.init_all([0])
         try:
-            ok = ES.run_cases(comm, 1, ES.small_shapes(), ES.SMALL_RUNS, lines.append)
+            ok = ES.run_cases(comm, 1, ES.small_shapes(), runs, lines.append)
         finally:
             comm.destroy()
     return {"returncode": 0 if ok else 1, "lines": lines, "secs": time.perf_counter() - t0, "stderr": ""}
@@ -86,7 +86,9 @@ def run_worker(nproc, args):
 
 def launch(key):
     """The records of one launch, made on first use. key: ("inproc", always_collect),
-    ("small", world) or ("panels", alg)."""
+    ("small", world) or ("panels", alg); for tests/test_gpu_engine_block_sequences.py, which shares
+    this cache and its stop rule: ("blk_inproc", always_collect), ("blocks", world) or
+    ("blocks", world, alg), or ("blockpanels", alg)."""
     if key not in _launches:
         if _stopped:
             _launches[key] = {"returncode": None, "lines": [], "secs": 0.0, "stderr": "not run: " + _stopped[0]}
@@ -96,8 +98,12 @@ def launch(key):
                     res = run_world_1(key[1])
                 elif key[0] == "small":
                     res = run_worker(key[1], ["small"])
+                elif key[0] == "blk_inproc":
+                    res = run_world_1(key[1], ES.BLOCK_RUNS)
+                elif key[0] == "blocks":
+                    res = run_worker(key[1], ["blocks"] + list(key[2:]))
                 else:
-                    res = run_worker(ES.PANEL_WORLD, ["panels", key[1]])
+                    res = run_worker(ES.PANEL_WORLD, [key[0], key[1]])
             except subprocess.TimeoutExpired as exc:
                 res = {"returncode": None, "lines": [], "secs": 110.0, "stderr": f"timed out: {exc}"}
             rc = res["returncode"]
