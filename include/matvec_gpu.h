@@ -209,7 +209,10 @@ const char* mvg_gemv_variant_name(int variant);
  * of nv products approaches that of one. Same numerics contract as mvg_gemv. */
 int mvg_gemv_multi(const double* d_A, int64_t lda, const double* d_X, int64_t ldx, double* d_Y,
                    int64_t ldy, int64_t m, int64_t k, int nv, void* stream);
-/* mvg_gemv_multi with an explicit kernel variant (0 = automatic; tests and sweeps) */
+/* mvg_gemv_multi with an explicit kernel variant (0 = automatic; tests and sweeps). A variant
+ * needs 16-B aligned A and X, even lda and ldx and k > 0; the LDS-DMA forms (mdma_r<RQ>_*,
+ * m16_r<RQ>_*: 16*RQ rows per workgroup) also 16*RQ * lda * 8 < 2^31 and nvec * ldx * 8 < 2^31
+ * (nvec 8, 16 for m16_*): MVG_E_INVALID otherwise, decided from the arguments alone. */
 int mvg_gemv_multi_variant(const double* d_A, int64_t lda, const double* d_X, int64_t ldx, double* d_Y,
                            int64_t ldy, int64_t m, int64_t k, int nv, int variant, void* stream);
 int mvg_gemv_multi_variant_count(void);
@@ -241,7 +244,9 @@ int mvg_multiply_std_rowwise(const double* matrix, const double* vector, int64_t
 /* explicit exact variant (0 = auto; names via mvg_gemv_exact_variant_name: seq_r<RW>_t<T>_b<NB>
  * and seqx_* RW-row LDS-DMA tiles of 2T columns with NB buffers, hop_l<L>_w<W>_u<U> L lanes per
  * row holding W columns each with U segments in flight, hop8_* the same with 8-B loads (any
- * alignment, any lda), seq_scalar a lane per row with 8-B loads) */
+ * alignment, any lda), seq_scalar a lane per row with 8-B loads). A variant whose operand rules the
+ * call breaks (seq_*, seqx_*, hop_*: 16-B aligned A and x, even lda; seq_*, seqx_*: lda < 2^23;
+ * hopxl_*: k <= 8192) is MVG_E_INVALID, decided from the arguments alone. */
 int mvg_gemv_exact_variant(const double* d_A, int64_t lda, const double* d_x, double* d_y,
                            int64_t m, int64_t k, int variant, void* stream);
 int mvg_gemv_exact_variant_count(void);

@@ -1795,12 +1795,19 @@ int mvg_gemv_multi_variant(const double* A, int64_t lda, const double* X, int64_
     if (m == 0 || nv == 0) return MVG_OK;
     if (!Y || ldy < m || (k > 0 && (!A || !X || lda < k || ldx < k)))
         return fail(MVG_E_INVALID, "mvg_gemv_multi: null pointer or leading dimension too small");
+    const bool vec = ((uintptr_t)A % 16 == 0) && ((uintptr_t)X % 16 == 0) && lda % 2 == 0 && ldx % 2 == 0;
+    // an explicit variant's operand rules are argument checks too: they answer before any HIP call
+    if (variant != 0) {
+        const MultiVariant& mv = kMultiVariants[variant];
+        if (!vec || k == 0)
+            return fail(MVG_E_INVALID, "mvg_gemv_multi: variants need even lda/ldx, 16-B aligned A, X");
+        if (mv.dma && !dma_ok(mv.rows_per_block, lda, ldx, mv.fn16 ? 16 : 8))
+            return fail(MVG_E_INVALID, "mvg_gemv_multi: lda or ldx too large for the DMA variant");
+    }
     if (int rc = take_pending_error("mvg_gemv_multi"); rc != MVG_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = ((uintptr_t)A % 16 == 0) && ((uintptr_t)X % 16 == 0) && lda % 2 == 0 && ldx % 2 == 0;
     if (!vec || k == 0) {  // odd lda/ldx or a view off 16 B (or k = 0): one vector at a time,
         // each through the single-vector dispatch (its unaligned 16-B forms, §4 "Odd widths")
-        if (variant != 0) return fail(MVG_E_INVALID, "mvg_gemv_multi: variants need even lda/ldx, 16-B aligned A, X");
         for (int v = 0; v < nv; ++v) {
             int rc = mvg_gemv_variant(A, lda, X + v * ldx, Y + v * ldy, m, k, 0, stream);
             if (rc != MVG_OK) return rc;

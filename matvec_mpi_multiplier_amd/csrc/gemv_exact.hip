@@ -1103,19 +1103,28 @@ int mvg_gemv_exact_variant(const double* A, int64_t lda, const double* x, double
         if (!A || !x) return fail(MVG_E_INVALID, "mvg_gemv_exact: null A or x");
         if (lda < k) return fail(MVG_E_INVALID, "mvg_gemv_exact: lda < k");
     }
+    // An explicit variant's operand rules are argument checks like the ones above: they answer
+    // first, with no HIP call at all (a host without a device gets the same answer).
+    const bool aligned = ((uintptr_t)A % 16 == 0) && ((uintptr_t)x % 16 == 0);
+    const auto refused = [&](int v) {
+        if (!operands_ok(kSeqVariants[v].needs, lda, aligned))
+            return fail(MVG_E_INVALID, kSeqVariants[v].needs == kVec16
+                                           ? "mvg_gemv_exact: 16-B variant needs 16-B aligned A, x and an even lda"
+                                           : "mvg_gemv_exact: LDS-DMA variant needs 16-B aligned A, x and an even lda < 2^23");
+        if (kSeqVariants[v].xlds && k > kXlMaxK)
+            return fail(MVG_E_INVALID, "mvg_gemv_exact: x-in-LDS variant needs k <= 8192");
+        return MVG_OK;
+    };
+    if (variant != 0)
+        if (int rc = refused(variant); rc != MVG_OK) return rc;
     // An error the caller's last HIP call left pending is that call's: reported here as it is
     // (this call fails, nothing launched), before any HIP call of ours (the dispatch's device
     // queries included) could replace it, and never mistaken for a refusal of the launch below.
     if (int rc = take_pending_error("mvg_gemv_exact"); rc != MVG_OK) return rc;
-    const bool aligned = ((uintptr_t)A % 16 == 0) && ((uintptr_t)x % 16 == 0);
     const bool lines = (uintptr_t)A % 128 == 0 && lda % 16 == 0;  // every row starts on a 128-B line
     const int v = variant == 0 ? pick_seq_variant(lda, m, k, aligned, lines) : variant;
-    if (!operands_ok(kSeqVariants[v].needs, lda, aligned))
-        return fail(MVG_E_INVALID, kSeqVariants[v].needs == kVec16
-                                       ? "mvg_gemv_exact: 16-B variant needs 16-B aligned A, x and an even lda"
-                                       : "mvg_gemv_exact: LDS-DMA variant needs 16-B aligned A, x and an even lda < 2^23");
+    if (int rc = refused(v); rc != MVG_OK) return rc;
     const SeqVariant& var = kSeqVariants[v];
-    if (var.xlds && k > kXlMaxK) return fail(MVG_E_INVALID, "mvg_gemv_exact: x-in-LDS variant needs k <= 8192");
     // k == 0 runs the kernel too: every row's sum stays 0 (the reference's `sum = 0`)
     // grid-size cap: fewer than 2^32 threads per launch
     const int64_t max_rows = exact_piece_rows(k, var.rows, (1ll << 32) / (64 * var.waves) - 1);
