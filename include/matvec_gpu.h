@@ -119,6 +119,19 @@ typedef struct mvg_xstep {
 int mvg_plan_exchange(int alg, int64_t R, int64_t C, int nranks, int rank, int force_collect,
                       mvg_xstep* steps, int max_steps, int* nsteps);
 
+/* The exchange after a local transposed product (mvg_gemv_t on each rank's shard): the mirror image of
+ * the schedule above on the same shards (mvg_plan_shard, the same divisibility refusals). The
+ * partial has n_cols doubles, the result C doubles on rank 0:
+ *   row  : REDUCE(world, count = C, PART -> Y)
+ *   col  : GATHER(world, count = C/P, key rank, PART -> Y)
+ *   block: REDUCE(comm MVG_X_COL: color grid_c, key grid_r, every rank a member; count = C/c,
+ *                 PART -> ROW on the grid_r == 0 leader),
+ *          GATHER(comm MVG_X_ROW: color 0, key grid_c, the grid-row-0 leaders; ROW -> Y)
+ *          (one grid row: a single GATHER(world, PART -> Y)).
+ * P == 1 has no steps unless force_collect != 0. */
+int mvg_plan_exchange_t(int alg, int64_t R, int64_t C, int nranks, int rank, int force_collect,
+                        mvg_xstep* steps, int max_steps, int* nsteps);
+
 /* Test hook: the calls one process driving `ndev` devices issues (the executables'
  * MVG_NGPUS=G form: ncclCommSplit of the schedule's sub-communicators, then one multiply's
  * exchange), produced by the engine's own exchange code with a recorder in place of RCCL, so no
@@ -312,6 +325,40 @@ int64_t mvg_exact_panel_width(int64_t m, int64_t k);
 int mvg_gemv_exact_panel_variant_count(void);
 int mvg_gemv_exact_panel_auto_variant(int64_t m, int64_t k);
 const char* mvg_gemv_exact_panel_variant_name(int variant);
+
+/* The transposed product on the same row-major A (beyond the reference, whose drivers only form
+ * A x; least squares, power iteration on A^T A and bidiagonalisation need both on one copy of A):
+ *   y[j] = sum_i A[i*lda + j] * z[i],  j < k, i < m   (lda >= k; z has m entries, y has k).
+ * Device pointers; asynchronous on `stream`. A is streamed once (csrc/gemv_t.hip): a workgroup
+ * sums a band of rows over a strip of columns, a lane per column, and a second kernel adds the
+ * bands out of the per-(device, stream) workspace mvg_gemv's split-K form also uses. Same accuracy
+ * contract as mvg_gemv: within 1e-12 relative per element of the sequential sum over i (what
+ * multiply_std_rowwise, src/matr_utils.c:86-96, gives on a transposed copy) on non-negative data.
+ * No atomics: FMAs in a fixed per-lane order, waves added in wave order, bands in band order
+ * within 16 runs of consecutive bands and the runs in run order, so y is the same bits from run to
+ * run whatever the workspace held. m == 0 writes k zeros, k == 0 is a no-op. Any lda >= k and any
+ * 8-byte alignment of A, z, y; nothing is read outside A[i, 0..k) and z[0..m) or stored outside
+ * y[0..k); a special value in column j of A reaches y[j] alone. */
+int mvg_gemv_t(const double* d_A, int64_t lda, const double* d_z, double* d_y, int64_t m, int64_t k, void* stream);
+/* explicit kernel variant (0 = auto; names via mvg_gemv_t_variant_name:
+ * strip_w<NW>_c<CPL>_u<UNR>_b<cap>: NW waves per workgroup, CPL columns per lane in 16-B loads,
+ * UNR rows in flight, bands of at most <cap> rows (256 unless named); scalar_*: the same with 8-B
+ * loads, a lane per column, which the automatic choice takes at any lda and alignment: they were
+ * the faster forms wherever swept). A launch is one grid of
+ * bands x strips workgroups; bands grow until it fits gridDim.x * blockDim.x < 2^32, and a k with
+ * more strips than one grid holds (2^31 / workgroup size of them) is MVG_E_INVALID, decided from the arguments alone
+ * before any HIP call. */
+int mvg_gemv_t_variant(const double* d_A, int64_t lda, const double* d_z, double* d_y, int64_t m, int64_t k,
+                       int variant, void* stream);
+int mvg_gemv_t_variant_count(void);
+/* the variant mvg_gemv_t picks for this lda, m and k (the pointers' alignment plays no part) */
+int mvg_gemv_t_auto_variant(int64_t lda, int64_t m, int64_t k);
+const char* mvg_gemv_t_variant_name(int variant);
+/* host only, decided from the arguments alone: how `variant` (0 = auto) cuts the problem into
+ * `bands` bands of `band_rows` rows (the last one shorter) and strips of `strip_cols` columns.
+ * One band: the sums go straight into y; more: 8 * bands * k bytes of workspace. */
+int mvg_gemv_t_plan(int64_t lda, int64_t m, int64_t k, int variant, int64_t* band_rows, int64_t* bands,
+                    int64_t* strip_cols);
 
 /* Read-only streaming microkernel over `bytes` of device memory (HBM ceiling calibration). */
 int mvg_stream_read(const double* d_src, int64_t n, double* d_sink, void* stream);

@@ -102,6 +102,8 @@ SIGNATURES = {
     "mvg_plan_shard": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, C.POINTER(Shard)]),
     "mvg_plan_exchange": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(XStep), C.c_int,
                                      C.POINTER(C.c_int)]),
+    "mvg_plan_exchange_t": (C.c_int, [C.c_int, _i64, _i64, C.c_int, C.c_int, C.c_int, C.POINTER(XStep), C.c_int,
+                                       C.POINTER(C.c_int)]),
     "mvg_synth_value": (C.c_double, [C.c_uint64, C.c_uint64]),
     "mvg_synth_fill_host": (C.c_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_uint64]),
     "mvg_synth_fill_device": (C.c_int, [_p, _i64, _i64, _i64, _i64, _i64, _i64, C.c_uint64, _p]),
@@ -152,6 +154,12 @@ SIGNATURES = {
     "mvg_gemv_exact_panel_variant_count": (C.c_int, []),
     "mvg_gemv_exact_panel_auto_variant": (C.c_int, [_i64, _i64]),
     "mvg_gemv_exact_panel_variant_name": (C.c_char_p, [C.c_int]),
+    "mvg_gemv_t": (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p]),
+    "mvg_gemv_t_variant": (C.c_int, [_p, _i64, _p, _p, _i64, _i64, C.c_int, _p]),
+    "mvg_gemv_t_variant_count": (C.c_int, []),
+    "mvg_gemv_t_auto_variant": (C.c_int, [_i64, _i64, _i64]),
+    "mvg_gemv_t_variant_name": (C.c_char_p, [C.c_int]),
+    "mvg_gemv_t_plan": (C.c_int, [_i64, _i64, _i64, C.c_int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "mvg_stream_read": (C.c_int, [_p, _i64, _p, _p]),
     "mvg_comm_unique_id": (C.c_int, [C.c_char_p]),
     "mvg_comm_init_all": (C.c_int, [C.POINTER(_p), C.c_int, C.POINTER(C.c_int)]),

@@ -70,6 +70,12 @@ int for_row_pieces(int64_t m, int64_t max_rows, F&& piece) {
     return MVG_OK;
 }
 
+// ----- the kernels' workspace (gemv.hip): n doubles of device memory that belong to `s` on the
+// current device, one buffer per (device, stream) grown on demand; the split-K partials of
+// mvg_gemv and the band partials of mvg_gemv_t (gemv_t.hip) both live there, each call's use
+// ending with its own last kernel on `s` (stream contract).
+int workspace(hipStream_t s, size_t n, double** out);
+
 // ----- exact exchange (gemv_exact.hip): the reference's own combine orders on the root
 // MPI_Reduce(SUM) as the reference's MPICH runs it (colwise.c:124): binomial tree or, for long
 // buffers, reduce-scatter + gather, by MPICH 3.3.2's own rule (gemv_exact.hip); overwrites parts

@@ -703,12 +703,13 @@ static int pick_variant(int64_t lda, int64_t M, int64_t K, bool aligned, bool al
     return kVecOneRow;
 }
 
-// Split-K workspace: one fp64 buffer per (device, stream), grown on demand (growth frees the
+// Split-K workspace (also the transposed product's band partials, gemv_t.hip; declared in
+// common.h): one fp64 buffer per (device, stream), grown on demand (growth frees the
 // old buffer, which hipFree synchronises); a split launch is not graph-capturable on first use.
 static std::mutex g_ws_mu;
 static std::map<std::pair<int, hipStream_t>, std::pair<double*, size_t>> g_ws;
 
-static int workspace(hipStream_t s, size_t n, double** out) {
+int workspace(hipStream_t s, size_t n, double** out) {
     int dev = 0;
     MVG_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_ws_mu);

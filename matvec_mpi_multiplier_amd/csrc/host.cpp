@@ -255,6 +255,52 @@ int mvg_plan_exchange(int alg, int64_t R, int64_t C, int P, int rank, int force,
     return MVG_OK;
 }
 
+// The mirror image for w = A^T z on the same shards: a shard's partial covers its n_cols columns
+// (w[col_off, +n_cols)), so the split that gathers forward reduces here and the other way round.
+int mvg_plan_exchange_t(int alg, int64_t R, int64_t C, int P, int rank, int force, mvg_xstep* steps,
+                        int max_steps, int* nsteps) {
+    if (!steps || !nsteps || max_steps < 0) return fail(MVG_E_INVALID, "mvg_plan_exchange_t: null");
+    *nsteps = 0;
+    mvg_shard s;
+    int rc = mvg_plan_shard(alg, R, C, P, rank, &s);
+    if (rc != MVG_OK) return rc;
+    if (P == 1 && !force) return MVG_OK;
+    mvg_xstep v[2];
+    int n = 1;
+    memset(v, 0, sizeof v);
+    v[0].comm = MVG_X_WORLD;
+    v[0].key = rank;
+    v[0].member = 1;
+    v[0].src = MVG_X_BUF_PART;
+    v[0].dst = MVG_X_BUF_Y;
+    v[0].count = s.n_cols;
+    if (alg == MVG_ALG_ROWWISE) {
+        v[0].op = MVG_X_REDUCE;
+    } else if (alg == MVG_ALG_COLWISE || s.grid_rows == 1) {
+        v[0].op = MVG_X_GATHER;
+    } else {
+        v[0].op = MVG_X_REDUCE;
+        v[0].comm = MVG_X_COL;
+        v[0].color = s.grid_c;
+        v[0].key = s.grid_r;
+        v[0].dst = MVG_X_BUF_ROW;
+        v[1].op = MVG_X_GATHER;
+        v[1].comm = MVG_X_ROW;
+        v[1].color = 0;
+        v[1].key = s.grid_c;
+        v[1].member = s.grid_r == 0;
+        v[1].root = 0;
+        v[1].src = MVG_X_BUF_ROW;
+        v[1].dst = MVG_X_BUF_Y;
+        v[1].count = s.n_cols;
+        n = 2;
+    }
+    if (n > max_steps) return fail(MVG_E_INVALID, "mvg_plan_exchange_t: steps buffer too small");
+    for (int i = 0; i < n; ++i) steps[i] = v[i];
+    *nsteps = n;
+    return MVG_OK;
+}
+
 // ------------------------------------------------------------------ synthetic (host)
 double mvg_synth_value(uint64_t seed, uint64_t idx) { return synth_value(splitmix64(seed), idx); }
 

@@ -52,6 +52,15 @@ def plan_exchange(alg, R: int, Cn: int, nranks: int, rank: int, force_collect: b
     return [steps[i] for i in range(n.value)]
 
 
+def plan_exchange_t(alg, R: int, Cn: int, nranks: int, rank: int, force_collect: bool = False) -> list[XStep]:
+    """The exchange after the local transposed product (mvg_plan_exchange_t)."""
+    steps = (XStep * _lib.MAX_XSTEPS)()
+    n = C.c_int()
+    check(lib.mvg_plan_exchange_t(_alg_id(alg), R, Cn, nranks, rank, int(force_collect), steps,
+                                  _lib.MAX_XSTEPS, C.byref(n)), "mvg_plan_exchange_t")
+    return [steps[i] for i in range(n.value)]
+
+
 # ------------------------------------------------------------------ text I/O
 def trace_exchange(alg, R: int, Cn: int, ndev: int, exact: bool = False) -> list[dict]:
     """The calls one process driving `ndev` devices issues for the exchange (communicator splits,
@@ -154,6 +163,36 @@ def gemv(d_A: int, lda: int, d_x: int, d_y: int, m: int, k: int, stream=None, va
         check(lib.mvg_gemv_exact_variant(d_A, lda, d_x, d_y, m, k, variant, stream), "mvg_gemv_exact")
     else:
         check(lib.mvg_gemv_variant(d_A, lda, d_x, d_y, m, k, variant, stream), "mvg_gemv")
+
+
+def gemv_t(d_A: int, lda: int, d_z: int, d_y: int, m: int, k: int, stream=None, variant: int = 0) -> None:
+    """y = A^T z on device pointers (the raw kernel: mvg_gemv_t; A row-major m x k, z m, y k)."""
+    check(lib.mvg_gemv_t_variant(d_A, lda, d_z, d_y, m, k, variant, stream), "mvg_gemv_t")
+
+
+def gemv_t_plan(lda: int, m: int, k: int, variant: int = 0) -> tuple[int, int, int]:
+    """(band_rows, bands, strip_cols): how mvg_gemv_t's `variant` (0 = auto) cuts an m x k problem."""
+    b, n, sc = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.mvg_gemv_t_plan(lda, m, k, variant, C.byref(b), C.byref(n), C.byref(sc)), "mvg_gemv_t_plan")
+    return b.value, n.value, sc.value
+
+
+def multiply_t(A: np.ndarray, z: np.ndarray, variant: int = 0) -> np.ndarray:
+    """A^T z on the GPU from host arrays (A m x k row-major, z m): copies them to the current
+    device, runs mvg_gemv_t on A as it lies (no transposed copy), returns the k sums."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    R, Cn = A.shape
+    if z.shape != (R,):
+        raise ValueError(f"z has shape {z.shape}, A has {R} rows")
+    dA, dz, dy = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(R).upload(z), DeviceBuffer(Cn)
+    try:
+        gemv_t(dA.ptr, Cn, dz.ptr, dy.ptr, R, Cn, None, variant)
+        check(lib.mvg_stream_sync(None), "sync")
+        return dy.download(Cn)
+    finally:
+        for b in (dA, dz, dy):
+            b.free()
 
 
 def multiply_multi(A: np.ndarray, X: np.ndarray, exact: bool = False) -> np.ndarray:
