@@ -360,6 +360,55 @@ const char* mvg_gemv_t_variant_name(int variant);
 int mvg_gemv_t_plan(int64_t lda, int64_t m, int64_t k, int variant, int64_t* band_rows, int64_t* bands,
                     int64_t* strip_cols);
 
+/* The fused normal-equations product on the same row-major A: what CGNR, LSQR-style solvers and power
+ * iteration on A^T A form every iteration, mvg_gemv and mvg_gemv_t back to back, in one call:
+ *   t[i] = sum_j A[i*lda + j] * x[j],  i < m
+ *   w[j] = sum_i A[i*lda + j] * t[i],  j < k, with t[i] the rounded value that was stored
+ * (lda >= k; x and w have k entries, t has m). Both t and w are always written. t meets mvg_gemv's
+ * accuracy contract against A x, and w meets mvg_gemv_t's against A^T (the returned t): w is
+ * defined on the stored t, so no compounded bound is needed.
+ * Device pointers; asynchronous on `stream`. The fused variants (csrc/gemv_ata.hip) stream A once
+ * for both products: a workgroup owns a band of whole rows, forms t[i] from the row it has just
+ * loaded, adds t[i] times that row to k column sums it keeps in registers, and the band reduce of
+ * mvg_gemv_t adds the bands out of the per-(device, stream) workspace (16 * bands * k bytes of
+ * traffic; one band goes straight into w). Algorithmic bytes 8 * (m*k + 2*k + m) + 16 * bands * k.
+ * No atomics: every sum has one fixed order for a given (variant, m, k), so t and w are the same
+ * bits from run to run whatever the workspace held. Any lda >= k and any 8-byte alignment of A, x,
+ * t and w; 64-bit row offsets; nothing is read outside A[i, 0..k) and x[0..k) or stored outside
+ * t[0..m) and w[0..k). No two operands may overlap: in particular w == x is not allowed (w is
+ * written while other workgroups still read x). Special values behave as in the composed pair: a
+ * NaN in A[i, j] makes t[i] NaN and no other entry of t, and through t[i] every entry of w.
+ * m == 0 writes k zeros to w and nothing to t; k == 0 writes m zeros to t and nothing to w; both
+ * zero is a no-op. MVG_E_INVALID, decided from the arguments alone before any HIP call (messages
+ * start "mvg_gemv_ata"): a negative size, lda < k, a null pointer where data would be touched, a
+ * variant out of range, an explicit fused variant on a k beyond its max_k, a grid that cannot fit
+ * (two_pass: more column strips than one launch of mvg_gemv_t holds). */
+int mvg_gemv_ata(const double* d_A, int64_t lda, const double* d_x, double* d_t, double* d_w, int64_t m, int64_t k,
+                 void* stream);
+/* explicit variant (0 = auto; names via mvg_gemv_ata_variant_name):
+ *   1 = two_pass: mvg_gemv into t, then mvg_gemv_t from t, both on `stream`; defines the result
+ *       for every shape and is the only form for a k beyond every fused cap;
+ *   wrow_w<NW>_c<CPL>_u<UNR>: a wave per row, NW waves per workgroup, CPL columns per lane
+ *       (k <= max_k = 64 * CPL), UNR rows of loads in flight per wave;
+ *   wgrow_w<NW>_c<CPL>_r<RB>: a workgroup per row, wave w owning columns [w * 64 * CPL, +64 * CPL)
+ *       (k <= max_k = 64 * NW * CPL), RB rows per barrier.
+ * The automatic choice takes a fused form only for a class of shapes where the sweep showed it more
+ * than 2 % faster than two_pass in both kept runs; everything else takes two_pass. The fused
+ * variants stay callable by number. */
+int mvg_gemv_ata_variant(const double* d_A, int64_t lda, const double* d_x, double* d_t, double* d_w, int64_t m,
+                         int64_t k, int variant, void* stream);
+int mvg_gemv_ata_variant_count(void);
+/* the variant mvg_gemv_ata picks for this lda, m and k (the pointers' alignment plays no part) */
+int mvg_gemv_ata_auto_variant(int64_t lda, int64_t m, int64_t k);
+const char* mvg_gemv_ata_variant_name(int variant);
+/* host only, decided from the arguments alone: how `variant` (0 = auto) cuts the m rows into
+ * `bands` bands of `band_rows` rows (the last one shorter; bands * band_rows >= m >
+ * (bands - 1) * band_rows), one workgroup each, and the widest k it takes. Bands shrink (down to
+ * 32 rows) until the grid fills the chip and grow until gridDim.x * blockDim.x < 2^32. two_pass
+ * reports band_rows = bands = 0 and max_k = INT64_MAX. */
+int mvg_gemv_ata_plan(int64_t lda, int64_t m, int64_t k, int variant, int64_t* band_rows, int64_t* bands,
+                      int64_t* max_k);
+
 /* Read-only streaming microkernel over `bytes` of device memory (HBM ceiling calibration). */
 int mvg_stream_read(const double* d_src, int64_t n, double* d_sink, void* stream);
 

@@ -72,9 +72,14 @@ int for_row_pieces(int64_t m, int64_t max_rows, F&& piece) {
 
 // ----- the kernels' workspace (gemv.hip): n doubles of device memory that belong to `s` on the
 // current device, one buffer per (device, stream) grown on demand; the split-K partials of
-// mvg_gemv and the band partials of mvg_gemv_t (gemv_t.hip) both live there, each call's use
-// ending with its own last kernel on `s` (stream contract).
+// mvg_gemv and the band partials of mvg_gemv_t (gemv_t.hip) and mvg_gemv_ata (gemv_ata.hip) live
+// there, each call's use ending with its own last kernel on `s` (stream contract).
 int workspace(hipStream_t s, size_t n, double** out);
+
+// ----- the band reduce of the transposed product (gemv_t.hip, gemvt_reduce): y[j] = the sum over
+// b < bands of partial[b*k + j], j < k, in one fixed order for a given band count; mvg_gemv_t and
+// the fused mvg_gemv_ata (gemv_ata.hip) both end with it when they cut m into more than one band
+int launch_band_reduce(const double* partial, int64_t bands, double* y, int64_t k, hipStream_t s);
 
 // ----- exact exchange (gemv_exact.hip): the reference's own combine orders on the root
 // MPI_Reduce(SUM) as the reference's MPICH runs it (colwise.c:124): binomial tree or, for long

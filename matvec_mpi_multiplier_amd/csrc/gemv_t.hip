@@ -255,6 +255,14 @@ static int plan_t(const TVariant& var, int64_t m, int64_t k, TPlan* out) {
     return MVG_OK;
 }
 
+// y[j] = sum_b partial[b*k + j] on s (declared in common.h: gemv_ata.hip adds its bands with it too)
+int launch_band_reduce(const double* partial, int64_t bands, double* y, int64_t k, hipStream_t s) {
+    const int64_t rblocks = (k + 63) / 64 < (1 << 20) ? (k + 63) / 64 : (1 << 20);
+    hipLaunchKernelGGL(gemvt_reduce, dim3((unsigned)rblocks), dim3(kReduceGroups * 64), 0, s, partial, bands, y, k);
+    MVG_HIP(hipGetLastError());
+    return MVG_OK;
+}
+
 static int launch_t(int v, const double* A, int64_t lda, const double* z, double* y, int64_t m, int64_t k,
                     hipStream_t s) {
     const TVariant& var = kTVariants[v];
@@ -269,11 +277,7 @@ static int launch_t(int v, const double* A, int64_t lda, const double* z, double
     hipLaunchKernelGGL(var.fn, dim3((unsigned)(p.bands * p.nstrips)), dim3(var.threads), 0, s, A, lda, z, out, m, k,
                        p.band_rows, (unsigned)p.nstrips, k);
     MVG_HIP(hipGetLastError());
-    if (p.bands > 1) {
-        const int64_t rblocks = (k + 63) / 64 < (1 << 20) ? (k + 63) / 64 : (1 << 20);
-        hipLaunchKernelGGL(gemvt_reduce, dim3((unsigned)rblocks), dim3(kReduceGroups * 64), 0, s, out, p.bands, y, k);
-        MVG_HIP(hipGetLastError());
-    }
+    if (p.bands > 1) return launch_band_reduce(out, p.bands, y, k, s);
     return MVG_OK;
 }
 

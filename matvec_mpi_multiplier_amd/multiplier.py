@@ -195,6 +195,38 @@ def multiply_t(A: np.ndarray, z: np.ndarray, variant: int = 0) -> np.ndarray:
             b.free()
 
 
+def gemv_ata(d_A: int, lda: int, d_x: int, d_t: int, d_w: int, m: int, k: int, stream=None, variant: int = 0) -> None:
+    """t = A x and w = A^T t on device pointers (the raw kernel: mvg_gemv_ata; A row-major m x k, x k,
+    t m, w k; one pass over A in the fused variants)."""
+    check(lib.mvg_gemv_ata_variant(d_A, lda, d_x, d_t, d_w, m, k, variant, stream), "mvg_gemv_ata")
+
+
+def gemv_ata_plan(lda: int, m: int, k: int, variant: int = 0) -> tuple[int, int, int]:
+    """(band_rows, bands, max_k): how mvg_gemv_ata's `variant` (0 = auto) cuts an m x k problem;
+    two_pass reports (0, 0, INT64_MAX)."""
+    b, n, mk = C.c_int64(), C.c_int64(), C.c_int64()
+    check(lib.mvg_gemv_ata_plan(lda, m, k, variant, C.byref(b), C.byref(n), C.byref(mk)), "mvg_gemv_ata_plan")
+    return b.value, n.value, mk.value
+
+
+def multiply_ata(A: np.ndarray, x: np.ndarray, variant: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """(A x, A^T (A x)) on the GPU from host arrays (A m x k row-major, x k): copies them to the
+    current device, runs mvg_gemv_ata on A as it lies, returns t (m) and w (k)."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    R, Cn = A.shape
+    if x.shape != (Cn,):
+        raise ValueError(f"x has shape {x.shape}, A has {Cn} columns")
+    dA, dx, dt, dw = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(Cn).upload(x), DeviceBuffer(R), DeviceBuffer(Cn)
+    try:
+        gemv_ata(dA.ptr, Cn, dx.ptr, dt.ptr, dw.ptr, R, Cn, None, variant)
+        check(lib.mvg_stream_sync(None), "sync")
+        return dt.download(R), dw.download(Cn)
+    finally:
+        for b in (dA, dx, dt, dw):
+            b.free()
+
+
 def multiply_multi(A: np.ndarray, X: np.ndarray, exact: bool = False) -> np.ndarray:
     """Y = A X for a k x nv block of vectors in one pass over A (mvg_gemv_multi); returns m x nv.
     exact=True (mvg_gemv_exact_multi): every column bit-identical to the reference's
