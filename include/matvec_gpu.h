@@ -360,6 +360,66 @@ const char* mvg_gemv_t_variant_name(int variant);
 int mvg_gemv_t_plan(int64_t lda, int64_t m, int64_t k, int variant, int64_t* band_rows, int64_t* bands,
                     int64_t* strip_cols);
 
+/* The transposed product for a block of vectors (what subspace iteration, block Lanczos and
+ * randomized range finders need beside mvg_gemv_multi), mvg_gemv_multi's layout mirrored:
+ *   Y[j + v*ldy] = sum_i A[i*lda + j] * Z[i + v*ldz],  j < k, i < m, v < nv
+ * A row-major m x k (lda >= k), Z m x nv column-major (vector v at d_Z + v*ldz, ldz >= m), Y k x nv
+ * column-major (vector v at d_Y + v*ldy, ldy >= k). Device pointers; asynchronous on `stream`; the
+ * band partials live in the per-(device, stream) workspace. The fused variants (csrc/gemv_t_multi.hip)
+ * send the vectors out in groups of the variant's chain count NV and stream A once per group: a
+ * workgroup sums a band of rows over a strip of columns, a lane per column with NV sums, row i's NV
+ * values of Z read as wave-uniform scalars; a second kernel adds the bands of the whole group. The
+ * last group may be shorter than NV (it runs the same kernel; its spare chains read the group's last
+ * vector again and are never stored); a single leftover vector goes through mvg_gemv_t.
+ * Accuracy: mvg_gemv_t's contract per column (within 1e-12 relative per element of the sequential
+ * sum over i on non-negative data). With `separate`, and for the single leftover vector of a fused
+ * variant, column v is bit-identical to mvg_gemv_t on z_v. A column that a fused group computes has
+ * bits that depend on A, z_v, the variant, m and k alone: not on the other vectors' values, on nv or
+ * the column's place in its group, or on what the workspace held. No atomics; deterministic from
+ * run to run.
+ * Any 8-byte alignment of A, Z and Y and any lda >= k, ldz >= m, ldy >= k; row and vector offsets
+ * are 64-bit; nothing is read outside A[i, 0..k) and Z[0..m, v) or stored outside Y[0..k, v),
+ * v < nv: the gaps between columns (ldy > k) and past the last column are not touched. No two
+ * operands may overlap. A special value in A[i, j] reaches row j of Y only, one in Z[i, v] column v
+ * of Y only. m == 0 writes k zeros into each of the nv columns; k == 0 or nv == 0 is a no-op, also
+ * on null pointers. There is no upper limit on nv. MVG_E_INVALID, decided from the arguments alone
+ * before any HIP call (messages start "mvg_gemv_t_multi"): a negative size or nv, lda < k, ldz < m
+ * or ldy < k, a null pointer where data would be touched, a variant out of range, more column
+ * strips than one grid holds (2^31 / workgroup size of them; mvg_gemv_t's own limit where a vector
+ * goes through it). */
+int mvg_gemv_t_multi(const double* d_A, int64_t lda, const double* d_Z, int64_t ldz, double* d_Y, int64_t ldy,
+                     int64_t m, int64_t k, int nv, void* stream);
+/* explicit variant (0 = auto; names via mvg_gemv_t_multi_variant_name):
+ *   1 = separate: one mvg_gemv_t per vector on `stream`; defines the result for every shape;
+ *   tstripm_w<NW>_c<CPL>_u<UNR>_v<NV>: NV chains per column, NW waves per workgroup, strips of
+ *       64 * CPL columns (8-B loads, a lane per 64-column stride), UNR consecutive rows per wave
+ *       and step.
+ * The automatic choice takes a fused variant only for a class of (m, k, nv) where a committed sweep
+ * showed it more than 2 % faster than separate in every kept run: m >= 16384, k >= 64 and
+ * m * k >= 2^28, the range that was swept. It chooses group by group, a variant with no more chains
+ * than vectors are left (16, then 8, from 128 columns on, then 4 and 2), so every
+ * group it launches is a full one and a last single vector goes through mvg_gemv_t; a column's
+ * bits are those of its group's variant. Everything else takes separate. The fused variants stay
+ * callable by number. */
+int mvg_gemv_t_multi_variant(const double* d_A, int64_t lda, const double* d_Z, int64_t ldz, double* d_Y,
+                             int64_t ldy, int64_t m, int64_t k, int nv, int variant, void* stream);
+int mvg_gemv_t_multi_variant_count(void);
+/* the variant mvg_gemv_t_multi picks for these sizes (the pointers' alignment plays no part) */
+int mvg_gemv_t_multi_auto_variant(int64_t lda, int64_t ldz, int64_t m, int64_t k, int nv);
+const char* mvg_gemv_t_multi_variant_name(int variant);
+/* host only, decided from the arguments alone: the first group that `variant` (0 = auto) cuts
+ * from nv vectors. *group is its vector count: min(nv, NV) for a fused variant while at least two
+ * vectors are left, else 1 (0 for nv == 0); auto: the group of the variant that
+ * mvg_gemv_t_multi_auto_variant names for nv; band_rows, bands and strip_cols describe that group's
+ * launch (bands * band_rows >= m > (bands - 1) * band_rows). A fused variant's bands are
+ * 128 * NV rows, so that the partials' traffic 16 * bands * k * NV stays within 2 % of A's
+ * 8 * m * k, shrink (down to 32 rows) until the grid has 512 workgroups and grow until
+ * gridDim.x * blockDim.x < 2^32; they do not depend on nv. separate, and a fused variant with one
+ * vector left, report what mvg_gemv_t_plan reports, with group = 1. Walk a call group by group by
+ * asking again with nv - *group. */
+int mvg_gemv_t_multi_plan(int64_t lda, int64_t m, int64_t k, int nv, int variant, int64_t* band_rows,
+                          int64_t* bands, int64_t* strip_cols, int* group);
+
 /* The fused normal-equations product on the same row-major A: what CGNR, LSQR-style solvers and power
  * iteration on A^T A form every iteration, mvg_gemv and mvg_gemv_t back to back, in one call:
  *   t[i] = sum_j A[i*lda + j] * x[j],  i < m

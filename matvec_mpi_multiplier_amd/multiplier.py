@@ -195,6 +195,42 @@ def multiply_t(A: np.ndarray, z: np.ndarray, variant: int = 0) -> np.ndarray:
             b.free()
 
 
+def gemv_t_multi(d_A: int, lda: int, d_Z: int, ldz: int, d_Y: int, ldy: int, m: int, k: int, nv: int, stream=None,
+                 variant: int = 0) -> None:
+    """Y = A^T Z on device pointers (the raw kernel: mvg_gemv_t_multi; A row-major m x k, Z m x nv and
+    Y k x nv column-major, vector v at d_Z + v*ldz and d_Y + v*ldy)."""
+    check(lib.mvg_gemv_t_multi_variant(d_A, lda, d_Z, ldz, d_Y, ldy, m, k, nv, variant, stream), "mvg_gemv_t_multi")
+
+
+def gemv_t_multi_plan(lda: int, m: int, k: int, nv: int, variant: int = 0) -> tuple[int, int, int, int]:
+    """(band_rows, bands, strip_cols, group): the first group mvg_gemv_t_multi's `variant` (0 = auto)
+    cuts from nv vectors and how it cuts the m x k problem for it; ask again with nv - group."""
+    b, n, sc, g = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+    check(lib.mvg_gemv_t_multi_plan(lda, m, k, nv, variant, C.byref(b), C.byref(n), C.byref(sc), C.byref(g)),
+          "mvg_gemv_t_multi_plan")
+    return b.value, n.value, sc.value, g.value
+
+
+def multiply_t_multi(A: np.ndarray, Z: np.ndarray, variant: int = 0) -> np.ndarray:
+    """Y = A^T Z for an m x nv block of vectors (mvg_gemv_t_multi) from host arrays; returns k x nv,
+    one column per vector. A goes to the current device as it lies (no transposed copy)."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    Z = np.asarray(Z, dtype=np.float64)
+    R, Cn = A.shape
+    if Z.ndim != 2 or Z.shape[0] != R:
+        raise ValueError(f"Z has shape {Z.shape}, A has {R} rows")
+    nv = Z.shape[1]
+    Zc = np.ascontiguousarray(Z.T)  # column-major: vector v contiguous
+    dA, dZ, dY = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(R * nv).upload(Zc), DeviceBuffer(Cn * nv)
+    try:
+        gemv_t_multi(dA.ptr, Cn, dZ.ptr, R, dY.ptr, Cn, R, Cn, nv, None, variant)
+        check(lib.mvg_stream_sync(None), "sync")
+        return dY.download(Cn * nv).reshape(nv, Cn).T.copy()
+    finally:
+        for b in (dA, dZ, dY):
+            b.free()
+
+
 def gemv_ata(d_A: int, lda: int, d_x: int, d_t: int, d_w: int, m: int, k: int, stream=None, variant: int = 0) -> None:
     """t = A x and w = A^T t on device pointers (the raw kernel: mvg_gemv_ata; A row-major m x k, x k,
     t m, w k; one pass over A in the fused variants)."""
