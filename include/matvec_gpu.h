@@ -420,6 +420,84 @@ const char* mvg_gemv_t_multi_variant_name(int variant);
 int mvg_gemv_t_multi_plan(int64_t lda, int64_t m, int64_t k, int nv, int variant, int64_t* band_rows,
                           int64_t* bands, int64_t* strip_cols, int* group);
 
+/* The bit-exact transposed product: y = A^T z on the row-major A (m x k, lda >= k) with the bits of
+ * the reference's sequential rounded sum,
+ *   y[j]: sum = +0.0; for i = 0 .. m-1: sum = round(sum + round(A[i*lda + j] * z[i]))
+ * the multiply and the add each rounded (no FMA), rows strictly in order: what multiply_std_rowwise
+ * (src/matr_utils.c:86-96) gives on a contiguous transposed copy of A. mvg_gemv_t promises that sum
+ * to 1e-12 with bits that depend on variant, band cut and shape; here y is the same bits for every
+ * variant, every shape, every lda, every 8-byte alignment and every run, so a transposed result can
+ * be compared with array_equal against a CPU run. mvg_gemv_exact followed by mvg_gemv_t_exact is
+ * the exact form of the A^T A pair (there is no fused exact mvg_gemv_ata, and the engine does not
+ * run transposed products).
+ * Device pointers; asynchronous on `stream`; no workspace. A chain cannot be cut into bands, so a
+ * workgroup owns a strip of columns over all m rows and a lane that owns a column carries its
+ * chain (csrc/gemv_t_exact.hip): the time is at least max(8*m*k / HBM rate, m chain steps).
+ * Nothing is read outside A[i, 0..k) and z[0..m), nothing is stored outside y[0..k); row offsets
+ * are 64-bit. m == 0 writes k values of +0.0; k == 0 is a no-op, also on null pointers. A special
+ * value in A[i, j] reaches y[j] alone; one in z[i] reaches every column, as the chain itself has it
+ * (0 * Inf = NaN in every column; signed zeros as the adds give them, +0.0 + -0.0 = +0.0).
+ * MVG_E_INVALID, decided from the arguments alone before any HIP call (messages start
+ * "mvg_gemv_t_exact"): a negative size, lda < k, a null pointer where data would be touched, a
+ * variant out of range, an explicit staged variant whose operand rules the call breaks, more column
+ * strips than one grid holds (2^31 / workgroup size of them). */
+int mvg_gemv_t_exact(const double* d_A, int64_t lda, const double* d_z, double* d_y, int64_t m, int64_t k,
+                     void* stream);
+/* explicit kernel variant (0 = auto; names via mvg_gemv_t_exact_variant_name):
+ *   1 = tseq_c64_u16, the direct form that defines the result: any lda, any 8-byte alignment;
+ *   tseq_c<SC>_u<U>: direct forms, a lane per column of a strip of SC columns, U rows of 8-byte
+ *       loads in flight in registers;
+ *   tseqx_w<NW>_c<SC>_t<T>_b<NB>: staged forms, NW waves fetch tiles of T rows x SC columns into a
+ *       ring of NB LDS buffers by LDS-DMA while SC chain lanes sum the tile before; they need A and
+ *       z 16-byte aligned, an even lda and lda < 2^29 / T (32-bit per-lane offsets over a tile's
+ *       rows), and are MVG_E_INVALID by number otherwise. The k % SC columns of a strip cut by k
+ *       go through variant 1 in a second launch on `stream`.
+ * The automatic choice takes another form than variant 1 only for a class of shapes where both
+ * kept sweep runs showed it more than 2 % ahead (m >= 16384, 64 <= k <= 32768, 2^28 <= m * k <= 2^31:
+ * a staged form by the width of k), and variant 1 wherever that form's operand rules are broken;
+ * every variant gives the same bits. */
+int mvg_gemv_t_exact_variant(const double* d_A, int64_t lda, const double* d_z, double* d_y, int64_t m, int64_t k,
+                             int variant, void* stream);
+int mvg_gemv_t_exact_variant_count(void);
+/* the variant mvg_gemv_t_exact picks for this lda, m and k on 16-byte aligned operands (operands
+ * 8 bytes off take variant 1 wherever this names a staged form) */
+int mvg_gemv_t_exact_auto_variant(int64_t lda, int64_t m, int64_t k);
+const char* mvg_gemv_t_exact_variant_name(int variant);
+/* host only: the variant mvg_gemv_t_exact runs for these operands, their alignment included: the
+ * pick of mvg_gemv_t_exact_auto_variant, or 1 where d_A, d_z or lda break that pick's rules */
+int mvg_gemv_t_exact_resolve_variant(const double* d_A, int64_t lda, const double* d_z, int64_t m, int64_t k);
+/* test hook: min_rows and min_size (m * k) stand in for the lower bounds of the swept range of the
+ * automatic choices of mvg_gemv_t_exact and mvg_gemv_t_exact_multi, so that a small problem takes
+ * the picks; 0 restores a bound */
+int mvg_debug_set_gemv_t_exact_swept(int64_t min_rows, int64_t min_size);
+
+/* The bit-exact transposed product for a block of vectors, in mvg_gemv_t_multi's layout and with
+ * its argument rules: A row-major m x k (lda >= k), Z m x nv column-major (vector v at d_Z + v*ldz,
+ * ldz >= m), Y k x nv column-major (vector v at d_Y + v*ldy, ldy >= k). Column v of Y is
+ * bit-identical to mvg_gemv_t_exact on z_v, whatever nv, the group and the other vectors are. The
+ * fused variants carry NV independent chains per column over one read of A and send the vectors
+ * out in groups of NV; a last group shorter than NV runs the same kernel (its spare chains read the
+ * group's last vector again and are never stored), a last single vector goes through
+ * mvg_gemv_t_exact. Nothing is read outside A[i, 0..k) and Z[0..m, v) or stored outside
+ * Y[0..k, v), v < nv. m == 0 writes k values of +0.0 into each column; k == 0 or nv == 0 is a
+ * no-op, also on null pointers. MVG_E_INVALID, decided from the arguments alone before any HIP call
+ * (messages start "mvg_gemv_t_exact_multi"): a negative size or nv, lda < k, ldz < m or ldy < k, a
+ * null pointer where data would be touched, a variant out of range, more column strips than one
+ * grid holds. */
+int mvg_gemv_t_exact_multi(const double* d_A, int64_t lda, const double* d_Z, int64_t ldz, double* d_Y, int64_t ldy,
+                           int64_t m, int64_t k, int nv, void* stream);
+/* explicit variant (0 = auto; names via mvg_gemv_t_exact_multi_variant_name):
+ *   1 = separate: one mvg_gemv_t_exact per vector on `stream`;
+ *   tseqm_c<SC>_u<U>_v<NV>: the direct form with NV chains per column.
+ * The automatic choice takes a fused form only where both kept sweep runs showed it more than 2 %
+ * ahead of separate; everything else takes separate. */
+int mvg_gemv_t_exact_multi_variant(const double* d_A, int64_t lda, const double* d_Z, int64_t ldz, double* d_Y,
+                                   int64_t ldy, int64_t m, int64_t k, int nv, int variant, void* stream);
+int mvg_gemv_t_exact_multi_variant_count(void);
+/* the variant mvg_gemv_t_exact_multi picks for the group that opens nv vectors */
+int mvg_gemv_t_exact_multi_auto_variant(int64_t lda, int64_t ldz, int64_t m, int64_t k, int nv);
+const char* mvg_gemv_t_exact_multi_variant_name(int variant);
+
 /* The fused normal-equations product on the same row-major A: what CGNR, LSQR-style solvers and power
  * iteration on A^T A form every iteration, mvg_gemv and mvg_gemv_t back to back, in one call:
  *   t[i] = sum_j A[i*lda + j] * x[j],  i < m

@@ -167,6 +167,18 @@ SIGNATURES = {
     "mvg_gemv_t_multi_variant_name": (C.c_char_p, [C.c_int]),
     "mvg_gemv_t_multi_plan": (C.c_int, [_i64, _i64, _i64, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64),
                                         C.POINTER(_i64), C.POINTER(C.c_int)]),
+    "mvg_gemv_t_exact": (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p]),
+    "mvg_gemv_t_exact_variant": (C.c_int, [_p, _i64, _p, _p, _i64, _i64, C.c_int, _p]),
+    "mvg_gemv_t_exact_variant_count": (C.c_int, []),
+    "mvg_gemv_t_exact_auto_variant": (C.c_int, [_i64, _i64, _i64]),
+    "mvg_gemv_t_exact_variant_name": (C.c_char_p, [C.c_int]),
+    "mvg_gemv_t_exact_resolve_variant": (C.c_int, [_p, _i64, _p, _i64, _i64]),
+    "mvg_debug_set_gemv_t_exact_swept": (C.c_int, [_i64, _i64]),
+    "mvg_gemv_t_exact_multi": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, C.c_int, _p]),
+    "mvg_gemv_t_exact_multi_variant": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, C.c_int, C.c_int, _p]),
+    "mvg_gemv_t_exact_multi_variant_count": (C.c_int, []),
+    "mvg_gemv_t_exact_multi_auto_variant": (C.c_int, [_i64, _i64, _i64, _i64, C.c_int]),
+    "mvg_gemv_t_exact_multi_variant_name": (C.c_char_p, [C.c_int]),
     "mvg_gemv_ata": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _p]),
     "mvg_gemv_ata_variant": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, C.c_int, _p]),
     "mvg_gemv_ata_variant_count": (C.c_int, []),

@@ -177,9 +177,17 @@ def gemv_t_plan(lda: int, m: int, k: int, variant: int = 0) -> tuple[int, int, i
     return b.value, n.value, sc.value
 
 
-def multiply_t(A: np.ndarray, z: np.ndarray, variant: int = 0) -> np.ndarray:
+def gemv_t_exact(d_A: int, lda: int, d_z: int, d_y: int, m: int, k: int, stream=None, variant: int = 0) -> None:
+    """y = A^T z on device pointers with the bits of the sequential rounded sum over the rows (the raw
+    kernel: mvg_gemv_t_exact; `variant` indexes its own table)."""
+    check(lib.mvg_gemv_t_exact_variant(d_A, lda, d_z, d_y, m, k, variant, stream), "mvg_gemv_t_exact")
+
+
+def multiply_t(A: np.ndarray, z: np.ndarray, variant: int = 0, exact: bool = False) -> np.ndarray:
     """A^T z on the GPU from host arrays (A m x k row-major, z m): copies them to the current
-    device, runs mvg_gemv_t on A as it lies (no transposed copy), returns the k sums."""
+    device, runs mvg_gemv_t on A as it lies (no transposed copy), returns the k sums. exact: the
+    bits of multiply_std_rowwise on a transposed copy (mvg_gemv_t_exact; `variant` then indexes the
+    exact table)."""
     A = np.ascontiguousarray(A, dtype=np.float64)
     z = np.ascontiguousarray(z, dtype=np.float64)
     R, Cn = A.shape
@@ -187,7 +195,7 @@ def multiply_t(A: np.ndarray, z: np.ndarray, variant: int = 0) -> np.ndarray:
         raise ValueError(f"z has shape {z.shape}, A has {R} rows")
     dA, dz, dy = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(R).upload(z), DeviceBuffer(Cn)
     try:
-        gemv_t(dA.ptr, Cn, dz.ptr, dy.ptr, R, Cn, None, variant)
+        (gemv_t_exact if exact else gemv_t)(dA.ptr, Cn, dz.ptr, dy.ptr, R, Cn, None, variant)
         check(lib.mvg_stream_sync(None), "sync")
         return dy.download(Cn)
     finally:
@@ -211,9 +219,18 @@ def gemv_t_multi_plan(lda: int, m: int, k: int, nv: int, variant: int = 0) -> tu
     return b.value, n.value, sc.value, g.value
 
 
-def multiply_t_multi(A: np.ndarray, Z: np.ndarray, variant: int = 0) -> np.ndarray:
+def gemv_t_exact_multi(d_A: int, lda: int, d_Z: int, ldz: int, d_Y: int, ldy: int, m: int, k: int, nv: int,
+                       stream=None, variant: int = 0) -> None:
+    """Y = A^T Z on device pointers, column v with the bits of mvg_gemv_t_exact on z_v (the raw kernel:
+    mvg_gemv_t_exact_multi; mvg_gemv_t_multi's layout)."""
+    check(lib.mvg_gemv_t_exact_multi_variant(d_A, lda, d_Z, ldz, d_Y, ldy, m, k, nv, variant, stream),
+          "mvg_gemv_t_exact_multi")
+
+
+def multiply_t_multi(A: np.ndarray, Z: np.ndarray, variant: int = 0, exact: bool = False) -> np.ndarray:
     """Y = A^T Z for an m x nv block of vectors (mvg_gemv_t_multi) from host arrays; returns k x nv,
-    one column per vector. A goes to the current device as it lies (no transposed copy)."""
+    one column per vector. A goes to the current device as it lies (no transposed copy). exact:
+    mvg_gemv_t_exact_multi (`variant` then indexes the exact multi table)."""
     A = np.ascontiguousarray(A, dtype=np.float64)
     Z = np.asarray(Z, dtype=np.float64)
     R, Cn = A.shape
@@ -223,7 +240,7 @@ def multiply_t_multi(A: np.ndarray, Z: np.ndarray, variant: int = 0) -> np.ndarr
     Zc = np.ascontiguousarray(Z.T)  # column-major: vector v contiguous
     dA, dZ, dY = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(R * nv).upload(Zc), DeviceBuffer(Cn * nv)
     try:
-        gemv_t_multi(dA.ptr, Cn, dZ.ptr, R, dY.ptr, Cn, R, Cn, nv, None, variant)
+        (gemv_t_exact_multi if exact else gemv_t_multi)(dA.ptr, Cn, dZ.ptr, R, dY.ptr, Cn, R, Cn, nv, None, variant)
         check(lib.mvg_stream_sync(None), "sync")
         return dY.download(Cn * nv).reshape(nv, Cn).T.copy()
     finally:
