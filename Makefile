@@ -12,10 +12,10 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Wall -Wno-unused-result
 CXXFLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include
 LDLIBS   := -L$(ROCM)/lib -lamdhip64 -lrccl -lpthread -Wl,-rpath,$(ROCM)/lib
 
-HIP_SRCS := $(CSRC)/gemv.hip $(CSRC)/gemv_exact.hip $(CSRC)/gemv_t.hip $(CSRC)/gemv_t_multi.hip $(CSRC)/gemv_t_exact.hip $(CSRC)/gemv_ata.hip
+HIP_SRCS := $(CSRC)/gemv.hip $(CSRC)/gemv_exact.hip $(CSRC)/gemv_t.hip $(CSRC)/gemv_t_multi.hip $(CSRC)/gemv_t_exact.hip $(CSRC)/gemv_ata.hip $(CSRC)/gemv_ata_multi.hip
 CXX_SRCS := $(CSRC)/host.cpp $(CSRC)/engine.cpp $(CSRC)/textio.cpp
-HDRS     := $(CSRC)/common.h $(CSRC)/lds_dma.h $(CSRC)/wave_sum.h include/matvec_gpu.h
-OBJS     := $(BUILD)/gemv.o $(BUILD)/gemv_exact.o $(BUILD)/gemv_t.o $(BUILD)/gemv_t_multi.o $(BUILD)/gemv_t_exact.o $(BUILD)/gemv_ata.o $(BUILD)/host.o $(BUILD)/engine.o $(BUILD)/textio.o
+HDRS     := $(CSRC)/common.h $(CSRC)/lds_dma.h $(CSRC)/wave_sum.h $(CSRC)/ata_row.h include/matvec_gpu.h
+OBJS     := $(BUILD)/gemv.o $(BUILD)/gemv_exact.o $(BUILD)/gemv_t.o $(BUILD)/gemv_t_multi.o $(BUILD)/gemv_t_exact.o $(BUILD)/gemv_ata.o $(BUILD)/gemv_ata_multi.o $(BUILD)/host.o $(BUILD)/engine.o $(BUILD)/textio.o
 APPS     := bin/multiplier_rowwise bin/multiplier_colwise bin/multiplier_blockwise
 
 # The executables' launcher (apps/launch.h): over MPI when one is installed (the image's MPICH
@@ -55,6 +55,9 @@ $(BUILD)/gemv_t_multi.o: $(CSRC)/gemv_t_multi.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/gemv_ata.o: $(CSRC)/gemv_ata.hip $(HDRS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(BUILD)/gemv_ata_multi.o: $(CSRC)/gemv_ata_multi.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # the bit-exact kernels must never fuse a*b + c (the reference rounds the product first)
@@ -103,8 +106,8 @@ $(ASAN_DIR):
 $(ASAN_DIR)/%.o: $(CSRC)/%.cpp $(HDRS) | $(ASAN_DIR)
 	$(CLANGXX) -std=c++17 -fPIC -Wall -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I$(ROCM)/include $(SANFLAGS) -c $< -o $@
 
-$(ASAN_DIR)/libmatvec_gpu.so: $(ASAN_OBJS) $(BUILD)/gemv.o $(BUILD)/gemv_exact.o $(BUILD)/gemv_t.o $(BUILD)/gemv_t_multi.o $(BUILD)/gemv_t_exact.o $(BUILD)/gemv_ata.o
-	$(CLANGXX) -shared -fPIC -shared-libasan $(SANFLAGS) $(BUILD)/gemv.o $(BUILD)/gemv_exact.o $(BUILD)/gemv_t.o $(BUILD)/gemv_t_multi.o $(BUILD)/gemv_t_exact.o $(BUILD)/gemv_ata.o $(ASAN_OBJS) -o $@ $(LDLIBS)
+$(ASAN_DIR)/libmatvec_gpu.so: $(ASAN_OBJS) $(BUILD)/gemv.o $(BUILD)/gemv_exact.o $(BUILD)/gemv_t.o $(BUILD)/gemv_t_multi.o $(BUILD)/gemv_t_exact.o $(BUILD)/gemv_ata.o $(BUILD)/gemv_ata_multi.o
+	$(CLANGXX) -shared -fPIC -shared-libasan $(SANFLAGS) $(BUILD)/gemv.o $(BUILD)/gemv_exact.o $(BUILD)/gemv_t.o $(BUILD)/gemv_t_multi.o $(BUILD)/gemv_t_exact.o $(BUILD)/gemv_ata.o $(BUILD)/gemv_ata_multi.o $(ASAN_OBJS) -o $@ $(LDLIBS)
 
 $(ASAN_DIR)/liboracle.so: oracle/cpu_ref.c oracle/cpu_ref.h | $(ASAN_DIR)
 	$(CLANGC) -std=c11 -fPIC -shared -shared-libasan -ffp-contract=off -pthread $(SANFLAGS) $< -o $@

@@ -547,6 +547,69 @@ const char* mvg_gemv_ata_variant_name(int variant);
 int mvg_gemv_ata_plan(int64_t lda, int64_t m, int64_t k, int variant, int64_t* band_rows, int64_t* bands,
                       int64_t* max_k);
 
+/* The fused normal-equations product for a block of vectors (what subspace iteration, block Lanczos
+ * and randomized range finders form in every step), in the layout of mvg_gemv_multi and
+ * mvg_gemv_t_multi:
+ *   T[i + v*ldt] = sum_j A[i*lda + j] * X[j + v*ldx],  i < m, v < nv
+ *   W[j + v*ldw] = sum_i A[i*lda + j] * T[i + v*ldt],  j < k, with the T[i, v] that was stored
+ * A row-major m x k (lda >= k); X k x nv, T m x nv and W k x nv column-major (vector v at d_X + v*ldx,
+ * d_T + v*ldt, d_W + v*ldw; ldx >= k, ldt >= m, ldw >= k). Both T and W are always written.
+ * Device pointers; asynchronous on `stream`: the fused kernel, the band reduce out of the
+ * per-(device, stream) workspace, every group, the single leftover vector, both halves of two_pass
+ * and the zeroings of the empty sums all run there. The fused variants (csrc/gemv_ata_multi.hip)
+ * send the vectors out in groups of the variant's chain count NV and stream A once per group: the
+ * kernels of mvg_gemv_ata with NV column sets, a loaded row serving all NV chains; the band reduce of
+ * mvg_gemv_t_multi adds the bands of the whole group in one launch. The last group may be shorter
+ * than NV (it runs the same kernel; its spare chains hold the group's last vector again and store
+ * nothing); a single leftover vector goes through mvg_gemv_ata (automatic).
+ * Accuracy: column v of T meets mvg_gemv's contract against A x_v, and column v of W meets
+ * mvg_gemv_t's against A^T (the returned column of T). No atomics: every sum has one fixed order
+ * for a given (kernel, m, k). A column's bits depend on A, x_v, m, k and the kernel that ran its
+ * group (the fused variant, or mvg_gemv_ata for a single leftover vector) alone: never on the other
+ * vectors' values, on the column's place in its group, or on what the workspace held. A NaN in
+ * X[j, v] or produced in T[i, v] stays in column v; a NaN in A[i, j] reaches row i of T in every
+ * column and, through it, all of W.
+ * Any 8-byte alignment and any leading dimensions within the rules above; row and vector offsets are
+ * 64-bit; nothing is read outside A[i, 0..k) and X[0..k, v) or stored outside T[0..m, v) and
+ * W[0..k, v), v < nv. No two operands may overlap. nv == 0 is a no-op; m == 0 writes k x nv zeros to
+ * W and nothing to T; k == 0 writes m x nv zeros to T and nothing to W; both zero is a no-op.
+ * MVG_E_INVALID, decided from the arguments alone before any HIP call (messages start
+ * "mvg_gemv_ata_multi"): a negative size or nv, lda < k, ldx < k, ldt < m or ldw < k, a null pointer
+ * where data would be touched, a variant out of range, an explicit fused variant on a k beyond its
+ * max_k, a grid that cannot fit (more column strips than one launch of the transposed half holds). */
+int mvg_gemv_ata_multi(const double* d_A, int64_t lda, const double* d_X, int64_t ldx, double* d_T, int64_t ldt,
+                       double* d_W, int64_t ldw, int64_t m, int64_t k, int nv, void* stream);
+/* explicit variant (0 = auto; names via mvg_gemv_ata_multi_variant_name):
+ *   1 = two_pass: mvg_gemv_multi into T, then mvg_gemv_t_multi from T, both automatic, on `stream`,
+ *       all nv vectors at once; defines the result for every shape, serves the empty sums and is
+ *       the only form for a k beyond every fused cap (8192);
+ *   wrowm_w<NW>_c<CPL>_u<UNR>_v<NV>: a wave per row, NW waves per workgroup, CPL columns per lane
+ *       (k <= max_k = 64 * CPL), UNR rows of loads in flight per wave, NV chains;
+ *   wgrowm_w<NW>_c<CPL>_r<RB>_v<NV>: a workgroup per row, wave w owning columns
+ *       [w * 64 * CPL, +64 * CPL) (k <= max_k = 64 * NW * CPL), RB rows per barrier, NV chains.
+ * The automatic choice goes group by group and names a fused form, with no more chains than vectors
+ * are left, only for a class of shapes where two kept sweep runs both showed it more than 2 % ahead
+ * of two_pass. No sweep has been run: the automatic choice is two_pass for every shape, and its last
+ * single vector (nv == 1 included) is mvg_gemv_ata bit for bit. The fused variants are callable by
+ * number. */
+int mvg_gemv_ata_multi_variant(const double* d_A, int64_t lda, const double* d_X, int64_t ldx, double* d_T, int64_t ldt,
+                               double* d_W, int64_t ldw, int64_t m, int64_t k, int nv, int variant, void* stream);
+int mvg_gemv_ata_multi_variant_count(void);
+/* the variant mvg_gemv_ata_multi picks for the group that opens nv vectors (the pointers' alignment
+ * plays no part; one vector alone goes through mvg_gemv_ata whatever this names) */
+int mvg_gemv_ata_multi_auto_variant(int64_t lda, int64_t ldx, int64_t m, int64_t k, int nv);
+const char* mvg_gemv_ata_multi_variant_name(int variant);
+/* host only, decided from the arguments alone: the first group that `variant` (0 = auto) cuts from
+ * nv vectors. *group is its vector count: min(nv, NV) for a fused variant while at least two
+ * vectors are left; nv for two_pass (the pair takes them all at once); 1 for a single leftover
+ * vector (0 for nv == 0). band_rows, bands and max_k describe that group's launch: mvg_gemv_ata_plan's
+ * rule per variant (bands * band_rows >= m > (bands - 1) * band_rows, one workgroup each), never a
+ * function of nv; two_pass reports band_rows = bands = 0 and max_k = INT64_MAX; a single vector
+ * reports what mvg_gemv_ata_plan reports for the automatic choice. Walk a call group by group by
+ * asking again with nv - *group. */
+int mvg_gemv_ata_multi_plan(int64_t lda, int64_t m, int64_t k, int nv, int variant, int64_t* band_rows, int64_t* bands,
+                            int64_t* max_k, int* group);
+
 /* Read-only streaming microkernel over `bytes` of device memory (HBM ceiling calibration). */
 int mvg_stream_read(const double* d_src, int64_t n, double* d_sink, void* stream);
 

@@ -80,6 +80,11 @@ int workspace(hipStream_t s, size_t n, double** out);
 // b < bands of partial[b*k + j], j < k, in one fixed order for a given band count; mvg_gemv_t and
 // the fused mvg_gemv_ata (gemv_ata.hip) both end with it when they cut m into more than one band
 int launch_band_reduce(const double* partial, int64_t bands, double* y, int64_t k, hipStream_t s);
+// the same for a group of g vectors in one launch (gemv_t_multi.hip, gemvtm_reduce): Y[j + v*ldy] =
+// the sum over b < bands of partial[v*vs + b*k + j], in launch_band_reduce's order per vector;
+// mvg_gemv_t_multi and the fused mvg_gemv_ata_multi (gemv_ata_multi.hip) both end with it
+int launch_band_reduce_multi(const double* partial, int64_t vs, int64_t bands, double* Y, int64_t ldy, int64_t k, int g,
+                             hipStream_t s);
 
 // ----- exact exchange (gemv_exact.hip): the reference's own combine orders on the root
 // MPI_Reduce(SUM) as the reference's MPICH runs it (colwise.c:124): binomial tree or, for long

@@ -176,6 +176,15 @@ __global__ __launch_bounds__(kMReduceGroups * 64) void gemvtm_reduce(const doubl
     }
 }
 
+int launch_band_reduce_multi(const double* partial, int64_t vs, int64_t bands, double* Y, int64_t ldy, int64_t k, int g,
+                             hipStream_t s) {
+    const int64_t rblocks = (k + 63) / 64 < (1 << 20) ? (k + 63) / 64 : (1 << 20);
+    hipLaunchKernelGGL(gemvtm_reduce, dim3((unsigned)rblocks, (unsigned)g), dim3(kMReduceGroups * 64), 0, s, partial, vs,
+                       bands, Y, ldy, k);
+    MVG_HIP(hipGetLastError());
+    return MVG_OK;
+}
+
 // ------------------------------------------------------------------ variant table
 typedef void (*gemvtm_fn)(const double*, int64_t, const double*, int64_t, double*, int64_t, int64_t, int64_t, int64_t,
                           int64_t, unsigned, int);
@@ -297,12 +306,7 @@ static int launch_tm(const MVariant& var, const MPlan& p, const double* A, int64
     hipLaunchKernelGGL(var.fn, dim3((unsigned)(p.bands * p.nstrips)), dim3(var.threads), 0, s, A, lda, Z, ldz, out,
                        out_vs, out_bs, m, k, p.band_rows, (unsigned)p.nstrips, g);
     MVG_HIP(hipGetLastError());
-    if (p.bands > 1) {
-        const int64_t rblocks = (k + 63) / 64 < (1 << 20) ? (k + 63) / 64 : (1 << 20);
-        hipLaunchKernelGGL(gemvtm_reduce, dim3((unsigned)rblocks, (unsigned)g), dim3(kMReduceGroups * 64), 0, s, out,
-                           out_vs, p.bands, Y, ldy, k);
-        MVG_HIP(hipGetLastError());
-    }
+    if (p.bands > 1) return launch_band_reduce_multi(out, out_vs, p.bands, Y, ldy, k, g, s);
     return MVG_OK;
 }
 

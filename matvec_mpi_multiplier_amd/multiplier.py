@@ -280,6 +280,46 @@ def multiply_ata(A: np.ndarray, x: np.ndarray, variant: int = 0) -> tuple[np.nda
             b.free()
 
 
+def gemv_ata_multi(d_A: int, lda: int, d_X: int, ldx: int, d_T: int, ldt: int, d_W: int, ldw: int, m: int, k: int,
+                   nv: int, stream=None, variant: int = 0) -> None:
+    """T = A X and W = A^T T on device pointers (the raw kernel: mvg_gemv_ata_multi; A row-major m x k,
+    X k x nv, T m x nv and W k x nv column-major, vector v at d_X + v*ldx, d_T + v*ldt, d_W + v*ldw;
+    one pass over A per group of vectors in the fused variants)."""
+    check(lib.mvg_gemv_ata_multi_variant(d_A, lda, d_X, ldx, d_T, ldt, d_W, ldw, m, k, nv, variant, stream),
+          "mvg_gemv_ata_multi")
+
+
+def gemv_ata_multi_plan(lda: int, m: int, k: int, nv: int, variant: int = 0) -> tuple[int, int, int, int]:
+    """(band_rows, bands, max_k, group): the first group mvg_gemv_ata_multi's `variant` (0 = auto) cuts
+    from nv vectors and how it cuts the m rows for it; two_pass reports (0, 0, INT64_MAX, nv). Ask
+    again with nv - group."""
+    b, n, mk, g = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int()
+    check(lib.mvg_gemv_ata_multi_plan(lda, m, k, nv, variant, C.byref(b), C.byref(n), C.byref(mk), C.byref(g)),
+          "mvg_gemv_ata_multi_plan")
+    return b.value, n.value, mk.value, g.value
+
+
+def multiply_ata_multi(A: np.ndarray, X: np.ndarray, variant: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """(A X, A^T (A X)) for a k x nv block of vectors (mvg_gemv_ata_multi) from host arrays; returns T
+    (m x nv) and W (k x nv), one column per vector. A goes to the current device as it lies."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    X = np.asarray(X, dtype=np.float64)
+    R, Cn = A.shape
+    if X.ndim != 2 or X.shape[0] != Cn:
+        raise ValueError(f"X has shape {X.shape}, A has {Cn} columns")
+    nv = X.shape[1]
+    Xc = np.ascontiguousarray(X.T)  # column-major: vector v contiguous
+    dA, dX = DeviceBuffer(R * Cn).upload(A), DeviceBuffer(Cn * nv).upload(Xc)
+    dT, dW = DeviceBuffer(R * nv), DeviceBuffer(Cn * nv)
+    try:
+        gemv_ata_multi(dA.ptr, Cn, dX.ptr, Cn, dT.ptr, R, dW.ptr, Cn, R, Cn, nv, None, variant)
+        check(lib.mvg_stream_sync(None), "sync")
+        return dT.download(R * nv).reshape(nv, R).T.copy(), dW.download(Cn * nv).reshape(nv, Cn).T.copy()
+    finally:
+        for b in (dA, dX, dT, dW):
+            b.free()
+
+
 def multiply_multi(A: np.ndarray, X: np.ndarray, exact: bool = False) -> np.ndarray:
     """Y = A X for a k x nv block of vectors in one pass over A (mvg_gemv_multi); returns m x nv.
     exact=True (mvg_gemv_exact_multi): every column bit-identical to the reference's
